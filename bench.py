@@ -8,11 +8,16 @@ With --gpus N (torchrun, one process per GPU) every rank evaluates its own hyper
 candidate per step (weak scaling) and the step ends with the sweep's one collective, an
 all-gather of the per-rank (nlml, info) pairs over RCCL.
 
-Prints ONE JSON line on rank 0 (fields per the driver contract) including
+A plain run sets up, warms up, times the steps and prints ONE JSON line on rank 0 (fields per the
+driver contract: metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  --dump-outputs DIR
+also writes what the last timed step computed as DIR/<name>.npy.  With --full the run goes on after the
+timed region and fills in the rest of the line:
   roofline      the trailing-update MFMA kernel (the dominant one): algorithmic flops of the
                 lower-triangular SYRK ÷ its HIP-event time over the timed region, vs the fp64
-                (or fp32) MFMA peak
+                (or fp32) MFMA peak (kbuild_roofline, kernel_ms_per_step: the same events passes)
   cpu_baseline  the numpy/SciPy restatement of the reference path (oracle/) timed on this host
+  check         the bench's own -LML values against the oracle (rel_vs_oracle), and with --dist the
+                all-gather of one more step (allgather_ok)
 """
 from __future__ import annotations
 
@@ -89,9 +94,16 @@ def parse():
     ap.add_argument("--chain", type=int, default=None,
                     help="single-member factorisations as one persistent launch (libgpk chain); default 0 when "
                          "--pipeline > 1, else the library default")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the CPU baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-events", action="store_true", help="time without per-kernel HIP events")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the per-kernel events and roofline passes, the CPU "
+                         "baseline and the oracle check of the bench's own values (with --dist: the all-gather "
+                         "check); a plain run does none of them and reports those fields as null")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (per candidate: nlml, fit, logdet, info; with "
+                         "--mode grad also gradient) as DIR/<name>.npy, float64")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="--full: budget of the CPU baseline sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-events", action="store_true", help="--full without the per-kernel HIP events passes")
     ap.add_argument("--roofline-steps", type=int, default=3, help="steps of the look-ahead-off roofline pass")
     ap.add_argument("--dist", action="store_true",
                     help="run the multi-GPU code path (RCCL process group, per-step all-gather, barriers, MAX "
@@ -105,8 +117,11 @@ def parse():
     ap.add_argument("--check-candidates", default=None,
                     help="comma-separated batch indices whose -LML is checked against the oracle after the "
                          "timed region (default: first, middle, last)")
-    ap.add_argument("--no-check", action="store_true", help="skip the oracle check of the bench's own values")
-    return ap.parse_args()
+    ap.add_argument("--no-check", action="store_true", help="--full without the oracle check of the bench's own values")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def free_port():
@@ -337,6 +352,19 @@ def oracle_check(cfg_name, n, rows, idx, kname, d, noise, got, known=None):
     return {"candidates": out, "rel_vs_oracle": max(r["rel"] for r in out)}
 
 
+def dump_outputs(path, fact, grad_mode):
+    """--dump-outputs: the arrays a caller of the timed path receives from one step's factorisation --
+    per candidate -LML, data fit, log-determinant and the factorisation's info (0 = success), with
+    --mode grad also d(-LML)/d(hyperparameters, noise) -- as <path>/<name>.npy, float64 (a few KB)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"nlml": fact.nlml(), "fit": fact.fit(), "logdet": fact.logdet(), "info": fact.info}
+    if grad_mode:
+        arrays["gradient"] = fact.gradient()
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(t.cpu().numpy(), dtype=np.float64))
+
+
 # Hardware queues per process: HIP multiplexes streams onto GPU_MAX_HW_QUEUES in-order hardware queues
 # (4 by default). P pipelined factorisation streams + torch's default stream + the comm stream + RCCL's stream
 # share them, and two streams sharing a queue serialise.  Measured with the RCCL path on (--dist, N = 8192,
@@ -565,8 +593,12 @@ def main():
         to = torch.tensor([timed_out], dtype=torch.int64, device=dev)
         dist.all_reduce(to, op=dist.ReduceOp.SUM)
         timed_out = int(to.item())
+    if args.dump_outputs:
+        # what the last timed step computed, as its caller receives it (every rank its own candidates)
+        dump_outputs(args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, "rank%d" % rank),
+                     facts[(step_no[0] - 1) % P], grad_mode)
     # per-class kernel spans of the production schedule (look-ahead on): a separate events pass
-    use_events = not args.no_events
+    use_events = args.full and not args.no_events
     timing = None
     if use_events:
         nat.timing_reset()
@@ -596,7 +628,7 @@ def main():
     nl = nl_all[0]
     info = int(fact.info.abs().max().item())
     gathered_ok = None
-    if use_dist:
+    if use_dist and args.full:
         # one more step on slot 0, gathered on its own: every rank's (nlml, info) pairs must have arrived via RCCL
         torch.cuda.synchronize()   # (the events passes' gathers are done with both buffers)
         pending.clear()
@@ -674,7 +706,7 @@ def main():
                                  "with the look-ahead the classes overlap" % args.roofline_steps)
         cpu = None
         cpu_nl0 = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             if grad_mode:
                 cpu = cpu_baseline_grad(args.config, n)
             else:
@@ -682,7 +714,7 @@ def main():
         # parity of the bench's own numbers: -LML of spread candidates against the oracle on the same inputs
         check = {"nlml": nl, "info": info, "chain_timeouts_timed": timed_out,
                  **({"allgather_ok": gathered_ok} if use_dist else {})}
-        if not args.no_check:
+        if args.full and not args.no_check:
             idx = ([int(v) for v in args.check_candidates.split(",")] if args.check_candidates else
                    sorted({0, batch // 2, batch - 1}))
             check.update(oracle_check(args.config, n, rows, idx, kname, d, noise, nl_all,

@@ -16,10 +16,12 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def run_bench(*args, timeout=100):
+def run_bench(*args, timeout=100, full=True):
+    """One bench.py child process; `full`: with --full (roofline passes, oracle and all-gather checks)."""
     env = dict(os.environ)
     env.setdefault("MASTER_PORT", "29563")
-    cp = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args], cwd=ROOT, env=env,
+    cp = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *(["--full"] if full else []), *args],
+                        cwd=ROOT, env=env,
                         capture_output=True, text=True, timeout=timeout)
     assert cp.returncode == 0, cp.stdout[-2000:] + cp.stderr[-4000:]
     lines = [l for l in cp.stdout.splitlines() if l.startswith("{")]
@@ -43,6 +45,34 @@ def test_bench_dist_rehearsal_metric():
     exp = o.nlml(("SE", {}), [0.1], 1e-2, x, y)
     assert abs(d["check"]["nlml"] - exp) <= 1e-9 * abs(exp)
     assert d["check"]["rel_vs_oracle"] <= 1e-9
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without --full: the headline fields only (no events passes, CPU baseline or oracle check), --steps timed
+    steps, and --dump-outputs writes the last timed step's per-candidate results as float64 .npy files, checked
+    here against the oracle (rel <= 1e-9, candidate c at lengthscale 0.1 (1 + 0.01 c))."""
+    import numpy as np
+    n, batch = 777, 3
+    out = tmp_path / "dump"
+    d = run_bench("--n", str(n), "--batch", str(batch), "--steps", "3", "--warmup", "1", "--dump-outputs", str(out),
+                  full=False)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert d["ms_per_step"] > 0 and abs(d["value"] - batch * 1000.0 / d["ms_per_step"]) <= 1e-3 * d["value"]
+    assert d["roofline"] is None and d["kbuild_roofline"] is None and d["kernel_ms_per_step"] is None
+    assert d["cpu_baseline"] is None and "rel_vs_oracle" not in d["check"] and d["check"]["info"] == 0
+    got = {f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))}
+    assert sorted(got) == ["fit", "info", "logdet", "nlml"]
+    assert all(a.dtype == np.float64 and a.shape == (batch,) for a in got.values())
+    assert not got["info"].any()
+    x, y = o.make_inputs("metric", n=n)
+    for c in range(batch):
+        exp = o.nlml(("SE", {}), [0.1 * (1.0 + 0.01 * c)], 1e-2, x, y)
+        assert abs(got["nlml"][c] - exp) <= 1e-9 * abs(exp)
+    # nlml = (fit + logdet + n log 2 pi) / 2 up to rounding of the three terms
+    total = 0.5 * (got["fit"] + got["logdet"] + n * np.log(2 * np.pi))
+    assert np.all(np.abs(got["nlml"] - total) <= 1e-12 * (np.abs(got["fit"]) + np.abs(got["logdet"]) + n * 2))
 
 
 def test_bench_dist_rehearsal_sweep():

@@ -1,4 +1,4 @@
-"""Summarise rocprofv3 PMC passes (gpurun_out/pmc/p*/run_counter_collection.csv) per kernel.
+"""Summarise rocprofv3 PMC passes (bench_out/pmc/p*/run_counter_collection.csv) per kernel.
 
 Prints, per kernel family, the mean over dispatches of each counter, plus derived figures:
 MFMA busy fraction, HBM bytes (FETCH_SIZE doubled per the gfx950 guide + WRITE_SIZE, in KiB
@@ -10,7 +10,7 @@ import glob
 import re
 import sys
 
-root = sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/pmc"
+root = sys.argv[1] if len(sys.argv) > 1 else "bench_out/pmc"
 
 
 def family(name):

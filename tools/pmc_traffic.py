@@ -17,7 +17,7 @@ import re
 import sys
 
 key = sys.argv[1]
-root = sys.argv[2] if len(sys.argv) > 2 else "gpurun_out/pmc"
+root = sys.argv[2] if len(sys.argv) > 2 else "bench_out/pmc"
 out = sys.argv[3] if len(sys.argv) > 3 else "profiles/pmc_traffic.json"
 
 per = collections.defaultdict(dict)   # dispatch id -> counter -> value

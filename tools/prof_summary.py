@@ -1,6 +1,6 @@
 """Group a rocprofv3 --kernel-trace --stats run into libgpk's timing classes.
 
-usage: python tools/prof_summary.py gpurun_out/prof/run_kernel_stats.csv [steps]
+usage: python tools/prof_summary.py bench_out/prof/run_kernel_stats.csv [steps]
 
 Prints per class (assemble / diag / trsm / update / finalize / trsv) the launch count, total and
 average duration, so the class averages can be checked against the HIP-event figures that

@@ -1,6 +1,6 @@
 """Timeline of one factorisation step from a rocprofv3 kernel trace.
 
-usage: python tools/trace_timeline.py gpurun_out/prof/run_kernel_trace.csv [step_index_from_end]
+usage: python tools/trace_timeline.py bench_out/prof/run_kernel_trace.csv [step_index_from_end]
 
 Steps are delimited by assemble_kernel dispatches.  Prints, for the chosen step, its wall span,
 the busy time of the bulk-update kernels, the time during which no update kernel runs (the

@@ -1,7 +1,7 @@
 """Split the update launches of the last look-ahead-off step of a rocprofv3 trace into the group
 (bulk, K = 128 G) launches and the in-group launches, with their achieved TF/s.
 
-usage: python tools/update_split.py gpurun_out/prof/run_kernel_trace.csv N BATCH [G] [INGROUP] [depth]
+usage: python tools/update_split.py bench_out/prof/run_kernel_trace.csv N BATCH [G] [INGROUP] [depth]
 INGROUP: 3 two-level left-looking (the default schedule for batches that fill the chip), 1 left-looking.
 Flops per launch: 2 K x (lower-triangle elements of the updated columns over the K rows), from the launch
 order of gpk_potrf_aug (gpk_abi.hip potrf_impl):

@@ -1,7 +1,8 @@
-"""Base kernels SE / PER / MAT32 / MAT52 (gpbasics/KernelBasics/BaseKernels.py) on the device.
+"""Base kernels SE / PER / MAT32 / MAT52 / LIN (gpbasics/KernelBasics/BaseKernels.py) on the device.
 
-One table-driven class body serves the four kernels on the hot path; each subclass only states
-its op code, its shape hyperparameters and its string name.  Semantics (formulae, DFS
+One table-driven class body serves the four stationary kernels on the hot path; each subclass only
+states its op code, its shape hyperparameters and its string name.  ``LinearKernel`` (the one
+non-stationary leaf) overrides the hyperparameter plumbing where it differs.  Semantics (formulae, DFS
 hyperparameter order, default values, bounds, names, |l| normalisation in
 ``set_last_hyper_parameter``) follow the reference:
 
@@ -9,6 +10,7 @@ hyperparameter order, default values, bounds, names, |l| normalisation in
   PER    hyp [l, p, (sg)]   BaseKernels.py:435-634
   MAT32  hyp [l, (sg)]      BaseKernels.py:697-851
   MAT52  hyp [l, (sg)]      BaseKernels.py:854-1011
+  LIN    hyp [c, (sg)]      BaseKernels.py:110-270   c a vector of input_dimensionality offsets
 
 ``sg`` exists only when ``global_parameters.p_scaled_base_kernel`` is True.
 
@@ -22,7 +24,12 @@ exp(-2 sum_d sin^2(pi |x_d - y_d| / p) / l^2).  Both equal the reference's L1 fo
 (BaseKernels.py:446, :708, :865) when D == 1; for D > 1 those L1 forms are not positive
 definite (their Cholesky fails on the SURVEY C3 / C5 inputs).  The default stays the reference form.
 
-Out of scope: LinearKernel, ConstantKernel (raises in the reference), WhiteNoiseKernel.
+``ConstantKernel`` exists and raises from its constructor, as the reference's does (BaseKernels.py:57).
+
+Out of scope: WhiteNoiseKernel.  The reference's form (BaseKernels.py:637-694) is an identity on the row /
+column INDEX, not a function of the points: it fails to broadcast for n != m and is all ones when
+min(n, m) = 1.  On the device that is a row / column index predicate in every leaf evaluator -- a change
+of its own.
 """
 from __future__ import annotations
 
@@ -255,3 +262,109 @@ class MaternKernel5_2(BaseKernel):
 
     def __init__(self, input_dimensionality: int, ard: bool = False, standard=None):
         super().__init__(k.KernelManifestation.MAT52, input_dimensionality, ard, standard)
+
+
+class LinearKernel(BaseKernel):
+    """sum_k (x_k - c_k)(y_k - c_k), times sg when scaled (BaseKernels.py:114-134): the device's GPK_OP_LIN leaf.
+
+    Hyperparameters [c, (sg)]: ``c`` is always a vector of ``input_dimensionality`` offsets, so there is no
+    ARD form (``ard=True`` raises).  Unlike the length scales, ``c`` is signed: no |.| normalisation, no positive
+    bounds, and ``get_last_hyper_parameter`` maps it back through the affine input scaling."""
+    _OP = nat.OP_LIN
+    _SHAPE = ("c",)
+    _ARD_CAPABLE = False
+
+    def __init__(self, input_dimensionality: int, ard: bool = False):
+        # the reference's signature is (input_dimensionality); ``ard`` exists only to say that there is no ARD form
+        # (ValueError from BaseKernel.__init__), as PeriodicKernel does.  No distance, so no ``standard`` option.
+        super().__init__(k.KernelManifestation.LIN, input_dimensionality, ard, None)
+
+    def uses_standard_form(self) -> bool:
+        return False
+
+    def _emit(self, nodes: list, offset: int, ard_slots: list, dim: int) -> int:
+        nodes.append((self._OP, offset, -1, nat.NODE_SCALED if global_param.p_scaled_base_kernel else 0))
+        return offset + self._n_values(dim)
+
+    def _n_values(self, dim: int) -> int:
+        return dim + (1 if global_param.p_scaled_base_kernel else 0)
+
+    def get_hyper_parameter_dimensionalities(self) -> List[list]:
+        """[[D], ([])] (BaseKernels.py:214-220)."""
+        dims = [[self.input_dimensionality]]
+        if global_param.p_scaled_base_kernel:
+            dims.append([])
+        return dims
+
+    def get_default_hyper_parameter(self, xrange: List[List[float]], n: int, from_distribution: bool = False):
+        """Fixed: c = 0.01 in every dimension, sg = 0.1 (BaseKernels.py:168-176).  Random: c uniform on
+        [min(x_min - range), max(x_max + range)], sg = |N(0.1, 0.2)| (:178-196), torch's generator."""
+        shape = [self.input_dimensionality]
+        if from_distribution:
+            lo = min(r[0] - (r[1] - r[0]) for r in xrange)
+            hi = max(r[1] + (r[1] - r[0]) for r in xrange)
+            out = [torch.empty(shape, dtype=torch.float64).uniform_(lo, hi)]
+            if global_param.p_scaled_base_kernel:
+                out.append(torch.abs(torch.normal(0.1, 0.2, size=[], dtype=torch.float64)))
+            return out
+        out = [torch.full(shape, 0.01, dtype=torch.float64)]
+        if global_param.p_scaled_base_kernel:
+            out.append(torch.tensor(0.1, dtype=torch.float64))
+        return out
+
+    def get_hyper_parameter_distribution_definition(self, xrange: List[List[float]], n: int) -> List[dict]:
+        """c uniform per input dimension on [x_min - range, x_max + range] (BaseKernels.py:198-212)."""
+        base = torch.as_tensor(xrange, dtype=torch.float64).reshape(-1, 2)
+        x_min, x_max = base[:, 0], base[:, 1]
+        x_range = x_max - x_min
+        out = [{"shape": [self.input_dimensionality], "minval": x_min - x_range, "maxval": x_max + x_range,
+                "type": "random_uniform"}]
+        if global_param.p_scaled_base_kernel:
+            out.append({"shape": [], "mean": 0.1, "stddev": 0.2, "type": "random_normal"})
+        return out
+
+    def get_hyper_parameter_bounds(self, xrange: List[List[float]], n: int) -> List[tuple]:
+        """c in (-inf, inf) per dimension; sg in [100 jitter, inf) (BaseKernels.py:136-151)."""
+        f64 = torch.float64
+        shape = [self.input_dimensionality]
+        out = [(torch.full(shape, -math.inf, dtype=f64), torch.full(shape, math.inf, dtype=f64))]
+        if global_param.p_scaled_base_kernel:
+            jit = float(torch.as_tensor(global_param.p_cov_matrix_jitter))
+            out.append((torch.tensor(jit * 100, dtype=f64), torch.tensor(math.inf, dtype=f64)))
+        return out
+
+    def set_last_hyper_parameter(self, last_hyper_parameter: List):
+        """Stored as given: the offsets are signed (BaseKernels.py:24-30; LinearKernel has no override)."""
+        if not isinstance(last_hyper_parameter, list):
+            raise Exception("Wrong type for last_hyper_parameter to be set!")
+        assert len(last_hyper_parameter) == self.get_number_of_hyper_parameter(), "Invalid hyper_param size: %s" % str(self)
+        self.last_hyper_parameter = list(last_hyper_parameter)
+
+    def get_last_hyper_parameter(self, scaling_x_param=None):
+        """c back in the unscaled inputs' coordinates, c * scale[1] + scale[0]; sg unchanged (BaseKernels.py:259-269)."""
+        result = self.last_hyper_parameter
+        if scaling_x_param is None or result is None:
+            return result
+        out = [result[0] * scaling_x_param[1] + scaling_x_param[0]]
+        if global_param.p_scaled_base_kernel:
+            out.append(result[1])
+        return out
+
+    def deepcopy(self):
+        c = LinearKernel(input_dimensionality=self.input_dimensionality)
+        if self.last_hyper_parameter is not None:
+            c.set_last_hyper_parameter(list(self.last_hyper_parameter))
+        if self.noise is not None:
+            c.set_noise(self.noise)
+        return c
+
+    def type_compare_to(self, other):
+        return isinstance(other, LinearKernel)
+
+
+class ConstantKernel(BaseKernel):
+    """Not available, as in the reference, whose constructor raises (BaseKernels.py:54-57)."""
+    _ARD_CAPABLE = False
+
+    def __init__(self, input_dimensionality: int):
+        raise Exception("Not up to date. Implementation for ConstantKernel is not available.")

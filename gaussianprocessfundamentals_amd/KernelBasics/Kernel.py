@@ -109,7 +109,8 @@ class Kernel(bgpc.Component):
     def get_derivative_matrices(self, hyper_parameter: List, x_vector, x_vector_) -> List:
         # not rebuilt: nothing in the reference calls them (its fitter differentiates through
         # tf.linalg.cholesky), SE's is wrong (K/BaseKernels.py:383-399), and the LML gradient is computed by
-        # the fused device pass of gpk_nlml_grad without any dK/dtheta matrix (LogLikelihood.get_metric_and_gradient)
+        # the fused device pass of gpk_nlml_grad without any dK/dtheta matrix (LogLikelihood.get_metric_and_gradient).
+        # LinearKernel's (get_c_derivative_matrix, K/BaseKernels.py:232-241) is not rebuilt either.
         raise NotImplementedError("analytic derivative matrices are not provided: use "
                                   "LogLikelihood.get_metric_and_gradient or autograd through get_metric")
 

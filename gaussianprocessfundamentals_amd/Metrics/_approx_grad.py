@@ -42,6 +42,8 @@ class NystroemAdjoint:
         d = int(X.shape[1])
         kd = engine.kernel_descriptor(kernel, d)
         dev = X.device
+        # k(x, x) is the same for every x unless the tree has a LIN leaf (the one non-stationary base kernel)
+        self.stationary = all(kd.nodes[q].op != engine.nat.OP_LIN for q in range(kd.n_nodes))
         self.hyp_bar = torch.zeros(kd.n_hyp, dtype=torch.float64, device=dev)
         self.noise_bar = torch.zeros((), dtype=torch.float64, device=dev)
         self.knm_bar = None
@@ -163,14 +165,34 @@ class NystroemAdjoint:
 
     def trace_correction(self, w: float):
         """trace(K_nm P K_mn + noise I - K): d/d K_nm = 2 K_nm P, d/d P = K_mn K_nm, d/d noise = n, and
-        -n d k(x, x) / d theta (stationary kernels: k(x, x) is the same for every x)."""
+        -sum_i d k(x_i, x_i) / d theta (diag_adjoint)."""
         knm, _, _, _, P = self.nystroem()
         self._acc_knm(engine.dgemm(knm, P), 2.0 * w)
         self._acc_p(engine.dgemm(knm, knm, trans_a=True), w)
         self.noise_bar.add_(torch.tensor(float(self.n), dtype=torch.float64, device=self.X.device), alpha=w)
-        one = torch.ones(1, dtype=torch.float64, device=self.X.device)
-        gh, _ = engine.kernel_vjp(self.kernel, self.hyp, self.X[:1], self.X[:1], gu=one, gv=one)
-        self.hyp_bar.add_(gh, alpha=-w * self.n)
+        self.hyp_bar.add_(self.diag_adjoint(), alpha=-w)
+
+    DIAG_CHUNK = 1024
+
+    def diag_adjoint(self) -> torch.Tensor:
+        """sum_i d k(x_i, x_i) / d theta, the adjoint of trace(K).  Stationary trees: k(x, x) is the same for every
+        x, so n times one point's.  A tree with a LIN leaf (k(x, x) = sg sum_k (x_k - c_k)^2 depends on x): the
+        kernel's reverse mode with identity weights over chunks of the training points (gpk_kernel_vjp skips the
+        zero weights; no n x n matrix)."""
+        dev = self.X.device
+        if self.stationary:
+            one = torch.ones(1, dtype=torch.float64, device=dev)
+            gh, _ = engine.kernel_vjp(self.kernel, self.hyp, self.X[:1], self.X[:1], gu=one, gv=one)
+            return gh * float(self.n)
+        B = min(self.DIAG_CHUNK, self.n)
+        eye = torch.eye(B, dtype=torch.float64, device=dev)
+        total = None
+        for i in range(0, self.n, B):
+            xc = self.X[i:i + B].contiguous()
+            b = int(xc.shape[0])
+            gh, _ = engine.kernel_vjp(self.kernel, self.hyp, xc, xc, G=eye[:b, :b])
+            total = gh.clone() if total is None else total + gh
+        return total
 
     def finish(self, want_z: bool):
         """Map the K_nm / P adjoints to (flat hyperparameter adjoint, noise adjoint, Z adjoint or None)."""

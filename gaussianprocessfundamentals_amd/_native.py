@@ -14,9 +14,9 @@ import torch  # noqa: F401  (must be loaded first: libgpk binds to torch's HIP r
 
 from . import _build
 
-GPK_ABI_VERSION = 6
+GPK_ABI_VERSION = 7
 GPK_F64, GPK_F32 = 0, 1
-OP_PER, OP_SE, OP_MAT32, OP_MAT52, OP_ADD, OP_MUL = 104, 105, 107, 108, 201, 202
+OP_LIN, OP_PER, OP_SE, OP_MAT32, OP_MAT52, OP_ADD, OP_MUL = 102, 104, 105, 107, 108, 201, 202
 NODE_SCALED, NODE_ARD, NODE_SE_EXPANDED, NODE_STANDARD = 1, 2, 4, 8
 MAX_NODES, MAX_DIM, MAX_ARD, MAX_HYP = 16, 16, 2, 64
 NUM_CLASSES = 7

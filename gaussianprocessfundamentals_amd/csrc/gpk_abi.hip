@@ -92,6 +92,14 @@ bool valid_kdesc(const gpk_kdesc* kd, int64_t d) {
     if (nd.op == GPK_OP_ADD || nd.op == GPK_OP_MUL) {
       if (sp < 2) return false;
       sp -= 1;
+    } else if (nd.op == GPK_OP_LIN) {
+      // one offset per input dimension (+ sg); the node reads the raw points: no ARD slot, no distance form
+      if (nd.flags & (GPK_NODE_ARD | GPK_NODE_SE_EXPANDED | GPK_NODE_STANDARD)) return false;
+      if (nd.ard_slot != -1) return false;
+      const int need = (int)d + ((nd.flags & GPK_NODE_SCALED) ? 1 : 0);
+      if (nd.hyp_offset < 0 || nd.hyp_offset + need > kd->n_hyp) return false;
+      sp += 1;
+      if (sp > 8) return false;
     } else if (nd.op == GPK_OP_SE || nd.op == GPK_OP_PER || nd.op == GPK_OP_MAT32 ||
                nd.op == GPK_OP_MAT52) {
       const bool ard = (nd.flags & GPK_NODE_ARD) != 0;
@@ -1468,7 +1476,8 @@ int gpk_nlml(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_dev, 
   if (!info_dev) return fail_arg(13, "info_dev");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   GPK_HIP(hipMemsetAsync(info_dev, 0, sizeof(int32_t) * lay->batch, s), "memset info");
-  // Fused K build (single-base-node kernels): only the first panel group's block columns are
+  // Fused K build (single SE / MAT32 / MAT52 nodes; any other single node, LIN included, takes the plain assemble
+  // launch and the unfused factorisation below): only the first panel group's block columns are
   // assembled; the first trailing update evaluates its C tiles instead of reading them, so the
   // trailing part of K is never written to HBM and read back.
   const Tune tn = tune_now();

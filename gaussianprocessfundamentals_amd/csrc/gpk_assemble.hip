@@ -17,6 +17,7 @@
 //   PER    KernelBasics/BaseKernels.py:440-457   exp((-2 sin^2(pi * (d1 / p))) / l^2)
 //   MAT32  KernelBasics/BaseKernels.py:702-720   (1 + f) e^-f,            f = (sqrt3 d1) / |l|
 //   MAT52  KernelBasics/BaseKernels.py:859-880   ((1 + f) + 5 d1^2 / (3 l^2)) e^-f,  f = (sqrt5 d1) / |l|
+//   LIN    KernelBasics/BaseKernels.py:114-134   (x - c)(y - c)^T over the dimensions, c one offset per dimension
 //   ADD/MUL KernelBasics/Operators.py:207-225, :306-326 (left fold over children)
 //   d1 = L1 distance (Auxiliary/Distances.py:10-12); SE distance either the expanded norm of
 //   Auxiliary/Distances.py:4-7 (GPK_NODE_SE_EXPANDED) or the direct sum of squares.
@@ -133,14 +134,19 @@ __device__ __forceinline__ void interior_single_sc(FastNode fn, const double* pr
 template <typename TOut, int D, int OP>
 __device__ __forceinline__ void interior_single(FastNode fn, const double* prow, const double* pcol, int dp, int c,
                                                 int r0, int64_t gi0, int64_t gj, double noise, TOut* W, int64_t ld) {
-  double cb[D];
+  double cb[D], cc[D];  // the lane's column point; a linear node's offsets (both in registers for the lane's rows)
 #pragma unroll
-  for (int k = 0; k < D; ++k) cb[k] = pcol[fn.off + c * dp + k];
+  for (int k = 0; k < D; ++k) {
+    cb[k] = pcol[fn.off + c * dp + k];
+    cc[k] = OP == GPK_OP_LIN ? fn.c[k] : 0.0;
+  }
   fn.op = OP;
   fn.d = D;
   for (int rr = r0; rr < ATILE; rr += 4) {
     const double* pa = prow + fn.off + rr * dp;
-    double v = GPK_ASM_ABLATE ? 0.0 : fast_value_at(fn, [pa](int k) { return pa[k]; }, [&cb](int k) { return cb[k]; });
+    double v = GPK_ASM_ABLATE ? 0.0
+                              : fast_value_at_c(fn, [pa](int k) { return pa[k]; }, [&cb](int k) { return cb[k]; },
+                                                [&cc](int k) { return cc[k]; });
     const int64_t gi = gi0 + rr;
     if (gi == gj) v += noise;
     W[gi * ld + gj] = (TOut)v;
@@ -206,13 +212,18 @@ __device__ __forceinline__ void leaf_rows(FastNode f, const double* prow, const 
                                           int mode, double (&acc)[ATILE / 4]) {
   f.op = OP;  // compile-time op: only its branch of fast_value_at is generated
   f.d = D;
-  double cb[D];
+  double cb[D], cc[D];
 #pragma unroll
-  for (int k = 0; k < D; ++k) cb[k] = pcol[f.off + c * dp + k];
+  for (int k = 0; k < D; ++k) {
+    cb[k] = pcol[f.off + c * dp + k];
+    cc[k] = OP == GPK_OP_LIN ? f.c[k] : 0.0;
+  }
 #pragma unroll
   for (int i = 0; i < ATILE / 4; ++i) {
     const double* pa = prow + f.off + (r0 + 4 * i) * dp;
-    const double v = GPK_ASM_ABLATE ? 0.0 : fast_value_at(f, [pa](int k) { return pa[k]; }, [&cb](int k) { return cb[k]; });
+    const double v = GPK_ASM_ABLATE ? 0.0
+                                    : fast_value_at_c(f, [pa](int k) { return pa[k]; }, [&cb](int k) { return cb[k]; },
+                                                      [&cc](int k) { return cc[k]; });
     acc[i] = mode == 0 ? v : (mode == 1 ? acc[i] + v : acc[i] * v);
   }
 }
@@ -247,7 +258,12 @@ __device__ __forceinline__ void leaf_dispatch(const FastNode& f, bool sc_on, con
     case GPK_OP_SE: leaf_rows<D, GPK_OP_SE>(f, prow, pcol, dp, c, r0, mode, acc); break;
     case GPK_OP_PER: leaf_rows<D, GPK_OP_PER>(f, prow, pcol, dp, c, r0, mode, acc); break;
     case GPK_OP_MAT32: leaf_rows<D, GPK_OP_MAT32>(f, prow, pcol, dp, c, r0, mode, acc); break;
-    default: leaf_rows<D, GPK_OP_MAT52>(f, prow, pcol, dp, c, r0, mode, acc); break;
+    case GPK_OP_MAT52: leaf_rows<D, GPK_OP_MAT52>(f, prow, pcol, dp, c, r0, mode, acc); break;
+    case GPK_OP_LIN: leaf_rows<D, GPK_OP_LIN>(f, prow, pcol, dp, c, r0, mode, acc); break;
+    default:  // (no such leaf passes valid_kdesc; were one to, NaN rather than another op's formula)
+#pragma unroll
+      for (int i = 0; i < ATILE / 4; ++i) acc[i] = NAN;
+      break;
   }
 }
 template <typename TOut, int D>
@@ -521,7 +537,8 @@ __device__ __forceinline__ bool interior_d(const gpk_kdesc& kd, const FastNode& 
       case GPK_OP_PER: interior_single<TOut, D, GPK_OP_PER>(fn, prow, pcol, dp, c, r0, gi0, gj, noise, W, ld); return true;
       case GPK_OP_MAT32: interior_single<TOut, D, GPK_OP_MAT32>(fn, prow, pcol, dp, c, r0, gi0, gj, noise, W, ld); return true;
       case GPK_OP_MAT52: interior_single<TOut, D, GPK_OP_MAT52>(fn, prow, pcol, dp, c, r0, gi0, gj, noise, W, ld); return true;
-      default: return false;
+      case GPK_OP_LIN: interior_single<TOut, D, GPK_OP_LIN>(fn, prow, pcol, dp, c, r0, gi0, gj, noise, W, ld); return true;
+      default: return false;  // (an op without an interior loop: the generic loop below evaluates it)
     }
   }
   if (TREE == 2) {
@@ -1221,6 +1238,21 @@ __device__ __forceinline__ void base_partials(const gpk_node& nd, const double* 
     }
     return;
   }
+  if (nd.op == GPK_OP_LIN) {
+    // k = sg sum_k (a_k - c_k)(b_k - c_k): d k / d c_k = -sg ((a_k - c_k) + (b_k - c_k)), d k / d sg the sum; the
+    // slots as an ARD node's (c in acc[0..d), sg in acc[GPK_MAX_DIM])
+    const double sg = scaled ? h[d] : 1.0;
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < GPK_MAX_DIM; ++k)
+      if (k < d) {
+        const double ta = a[k] - h[k], tb = b[k] - h[k];
+        s += ta * tb;
+        acc[k] -= coef * sg * (ta + tb);
+      }
+    if (scaled) acc[GPK_MAX_DIM] += coef * s;
+    return;
+  }
   if (nd.op == GPK_OP_PER) {
     const double l = h[0], per = h[1];
     double sn, tw;  // sum sin^2(theta), sum theta sin(2 theta)
@@ -1374,9 +1406,10 @@ __global__ __launch_bounds__(256) void grad_kernel(gpk_kdesc kd, AsmArgs a, Grad
     }
     // hyperparameter slots of this node: ARD l_0..l_{d-1} then sg (stored at acc[GPK_MAX_DIM])
     const bool ard = (nd.flags & GPK_NODE_ARD) != 0;
-    const int nshape = ard ? a.d : (nd.op == GPK_OP_PER ? 2 : 1);
+    const bool vec = ard || nd.op == GPK_OP_LIN;  // d vector entries (ARD l, LIN c), then sg
+    const int nshape = vec ? a.d : (nd.op == GPK_OP_PER ? 2 : 1);
     const bool scaled = (nd.flags & GPK_NODE_SCALED) != 0;
-    const bool sg_moved = ard && scaled;
+    const bool sg_moved = vec && scaled;
     const int np = nshape + (scaled ? 1 : 0);
 #pragma unroll
     for (int k = 0; k < GNP; ++k) {
@@ -1432,6 +1465,13 @@ __device__ __forceinline__ void base_input_partials(const gpk_node& nd, const do
   const bool ard = (fl & GPK_NODE_ARD) != 0;
   const bool scaled = (fl & GPK_NODE_SCALED) != 0;
   const double* h = hyp + nd.hyp_offset;
+  if (nd.op == GPK_OP_LIN) {  // d k / d b_k = sg (a_k - c_k)
+    const double sg = scaled ? h[d] : 1.0;
+#pragma unroll
+    for (int k = 0; k < GPK_MAX_DIM; ++k)
+      if (k < d) acc[k] += coef * sg * (a[k] - h[k]);
+    return;
+  }
   const double v = base_value(nd, hyp, a, b, d);  // includes sg
   if (nd.op == GPK_OP_SE) {
     const double l = ard ? 1.0 : h[0];
@@ -1557,9 +1597,10 @@ __global__ __launch_bounds__(256) void vjp_kernel(gpk_kdesc kd, AsmArgs a, VjpAr
 #pragma unroll
     for (int k = 0; k < GPK_MAX_DIM; ++k)
       if (k < a.d) gz[k] += ard ? az[k] / hyp_s[nd.hyp_offset + k] : az[k];
-    const int nshape = ard ? a.d : (nd.op == GPK_OP_PER ? 2 : 1);
+    const bool vec = ard || nd.op == GPK_OP_LIN;  // d vector entries (ARD l, LIN c), then sg
+    const int nshape = vec ? a.d : (nd.op == GPK_OP_PER ? 2 : 1);
     const bool scaled = (nd.flags & GPK_NODE_SCALED) != 0;
-    const bool sg_moved = ard && scaled;
+    const bool sg_moved = vec && scaled;
     const int np = nshape + (scaled ? 1 : 0);
 #pragma unroll
     for (int k = 0; k < GNP; ++k) {
@@ -1811,6 +1852,7 @@ hipError_t launch_assemble(const gpk_kdesc& kd, const AsmArgs& a, int dtype, int
     const gpk_node nd = kd.nodes[0];
     const bool se = nd.op == GPK_OP_SE && !(nd.flags & GPK_NODE_SE_EXPANDED);
     const bool mat = nd.op == GPK_OP_MAT32 || nd.op == GPK_OP_MAT52;
+    // (any other single node -- PER, the expanded SE, LIN -- has no f32 kernel: the general instantiation below)
     // every tile interior (training rows and columns) or tail (y / zero rows): n = n_pad, no test, identity or
     // dense rows, no ragged members -- then no edge tile can occur and the kernel runs alone (no list, no memset)
     const bool no_edges = a.n == a.n_pad && a.m == 0 && !a.nb && !a.mb && !a.eye && a.E == nullptr &&

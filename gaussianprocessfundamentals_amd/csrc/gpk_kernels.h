@@ -82,6 +82,16 @@ __device__ __forceinline__ void base_values(const gpk_node& nd, const double* __
 #pragma unroll
     for (int i = 0; i < R; ++i) r[i] = exp((-2.0 * sn[i]) / (l * l));
     sg_at = 2;
+  } else if (nd.op == GPK_OP_LIN) {  // sum_k (a_k - c_k)(b_k - c_k), c = h[0..d): the raw points, no ARD slot
+#pragma unroll
+    for (int i = 0; i < R; ++i) r[i] = 0.0;
+    for (int k = 0; k < d; ++k) {
+      const double ck = h[k];
+      const double tb = b[k] - ck;
+#pragma unroll
+      for (int i = 0; i < R; ++i) r[i] += (a[i][k] - ck) * tb;
+    }
+    sg_at = d;
   } else {  // MAT32 / MAT52
     double dist[R];
 #pragma unroll
@@ -162,6 +172,7 @@ struct Stack {
 struct FastNode {
   int op, flags, d, off;
   double il, il2, i3l2, iper, sg;
+  const double* c;  // linear node: its d offsets (the node's hyperparameters where the caller staged them)
   // periodic node through the staged sin / cos of its points (sc_node): sin(pi u), cos(pi u) per point and
   // dimension at offsets sc_sin / sc_cos from the point (tiles whose points all have |u| = |x / p| <= 4)
   int sc, sc_sin, sc_cos;
@@ -191,10 +202,15 @@ __device__ __forceinline__ FastNode make_fast_node(const gpk_node& nd, const dou
   const bool ard = (nd.flags & GPK_NODE_ARD) != 0;
   double l = 1.0;
   int sg_at = 1;
+  f.c = nullptr;
   if (nd.op == GPK_OP_PER) {
     l = h[0];
     f.iper = 1.0 / h[1];
     sg_at = 2;
+  } else if (nd.op == GPK_OP_LIN) {  // no length scale: hyp [c_0..c_{d-1}, (sg)]
+    f.c = h;
+    f.iper = 0.0;
+    sg_at = d;
   } else {
     l = ard ? 1.0 : (nd.op == GPK_OP_SE ? h[0] : fabs(h[0]));
     f.iper = 0.0;
@@ -254,9 +270,10 @@ __device__ __forceinline__ double sin2_pi(double t) {
   return sv * sv;
 }
 
-// fast_value over coordinate accessors: a(k), b(k) return coordinate k of the two points
-template <typename PA, typename PB>
-__device__ __forceinline__ double fast_value_at(const FastNode& f, PA a, PB b) {
+// fast_value over coordinate accessors: a(k), b(k) return coordinate k of the two points, c(k) offset k of a
+// linear node (read by that node only: callers that hold the offsets in registers pass them here)
+template <typename PA, typename PB, typename PC>
+__device__ __forceinline__ double fast_value_at_c(const FastNode& f, PA a, PB b, PC c) {
 #pragma clang fp contract(on)  // fuse within an expression only: every caller rounds alike
   const int d = f.d;
   double r;
@@ -288,6 +305,12 @@ __device__ __forceinline__ double fast_value_at(const FastNode& f, PA a, PB b) {
       sn = sin2_pi(dist * f.iper);
     }
     r = exp((-2.0 * sn) * f.il2);
+  } else if (f.op == GPK_OP_LIN) {
+    // the first non-stationary leaf: both points shifted by c, the products accumulated in k order (one fma
+    // per term: |error| <= (d + 2) eps / 2 sum_k |a_k - c_k| |b_k - c_k|).  Where the caller holds b and
+    // c in registers, (b_k - c_k) is invariant over the lane's rows: hoisting it is left to the compiler
+    r = 0.0;
+    for (int k = 0; k < d; ++k) r += (a(k) - c(k)) * (b(k) - c(k));
   } else {
     double dist = 0.0;
     if (f.flags & GPK_NODE_STANDARD) {
@@ -308,6 +331,12 @@ __device__ __forceinline__ double fast_value_at(const FastNode& f, PA a, PB b) {
     }
   }
   return f.sg * r;
+}
+
+template <typename PA, typename PB>
+__device__ __forceinline__ double fast_value_at(const FastNode& f, PA a, PB b) {
+  const double* cc = f.c;
+  return fast_value_at_c(f, a, b, [cc](int k) { return cc[k]; });
 }
 
 __device__ __forceinline__ double fast_value(const FastNode& f, const double* a, const double* b, bool sc_on = false) {

@@ -59,13 +59,15 @@
 extern "C" {
 #endif
 
-#define GPK_ABI_VERSION 6
+#define GPK_ABI_VERSION 7
 
 /* arithmetic types of the factorisation */
 enum { GPK_F64 = 0, GPK_F32 = 1 };
 
 /* kernel-tree op codes: values follow KernelManifestation (KernelBasics/Kernel.py:23-37) */
 enum {
+  GPK_OP_LIN = 102, /* sum_k (x_k - c_k)(y_k - c_k) (KernelBasics/BaseKernels.py:114-134): hyp [c_0..c_{dim-1}, (sg)];
+                       flags GPK_NODE_SCALED or 0 only (no ARD, expanded or standard form), ard_slot -1 */
   GPK_OP_PER = 104,
   GPK_OP_SE = 105,
   GPK_OP_MAT32 = 107,

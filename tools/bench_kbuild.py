@@ -2,9 +2,12 @@
 tiles written, and element rate, for the SURVEY configs whose K build is not fused into the first
 trailing update.
 
-usage: python tools/bench_kbuild.py [case ...]   (cases: C5, C3, SE8192; default all)
+usage: python tools/bench_kbuild.py [case ...]   (cases: C5, C3, SE8192, LIN; default C5 C3 SE8192)
 C5: ADD(SE-ARD, PER standard) D=8, N=16384 fp64; C3: MAT52-ARD D=4, N=8192 fp32; SE8192: SE D=1, N=8192
 fp64 batch 32 (the metric's inputs, built unfused).  Median of 10 launches, HIP events on the stream.
+LIN: the single-node LIN build against the single-node SE build through the same plain assemble launch, N = 8192,
+D = 1 and D = 8, fp64 and fp32 out (gpk_tune asm_f32_fast 0 for both, so SE's f32 build takes the same path): the
+two kernels alternate inside one run, 20 samples of 10 launches each; median, min and max (the run's own spread).
 """
 import ctypes
 import hashlib
@@ -66,6 +69,65 @@ def run(case):
             "Gelem_per_s": round(batch * n * (n + 1) / 2 / (ms * 1e-3) / 1e9, 2), "w0": digest}
 
 
+def run_leaves(n=8192, samples=20, inner=10):
+    """Rows for SE and LIN (one node each) at D = 1 / 8, fp64 / fp32 out, alternating inside each sample."""
+    from gaussianprocessfundamentals_amd.KernelBasics import BaseKernels as bk
+    dev = torch.device("cuda", 0)
+    L = nat.lib()
+    s = nat.stream_handle(dev)
+    rows = []
+    old = nat.tune("asm_f32_fast", 0)
+    try:
+        for dtype, dtn in ((torch.float64, "f64"), (torch.float32, "f32")):
+            for d in (1, 8):
+                g = torch.Generator().manual_seed(7)
+                X = torch.rand(n, d, generator=g, dtype=torch.float64).to(dev).contiguous()
+                Y = torch.rand(1, n, generator=g, dtype=torch.float64).to(dev).contiguous()
+                NZ = torch.tensor([0.1], dtype=torch.float64, device=dev)
+                f = engine.AugmentedFactorization(n, d, 0, 1, dtype)
+                lay = f.layout
+                progs = {}
+                for name, kern in (("SE", bk.SquaredExponentialKernel(d)), ("LIN", bk.LinearKernel(d))):
+                    kd = engine.kernel_descriptor(kern, d)
+                    H = (0.3 + torch.rand(1, kd.n_hyp, generator=g, dtype=torch.float64)).to(dev).contiguous()
+                    progs[name] = (kd, H)
+
+                def asm(name):
+                    kd, H = progs[name]
+                    nat.check(L.gpk_assemble(ctypes.byref(kd), ctypes.byref(lay), nat.ptr(H), kd.n_hyp, nat.ptr(NZ), 0,
+                                             nat.ptr(X), 0, None, 0, None, 0, nat.ptr(Y), 0, nat.ptr(f.W), s),
+                              "gpk_assemble")
+
+                for name in progs:
+                    for _ in range(3):
+                        asm(name)
+                torch.cuda.synchronize()
+                ts = {name: [] for name in progs}
+                for _ in range(samples):
+                    for name in progs:
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        for _ in range(inner):
+                            asm(name)
+                        e1.record()
+                        torch.cuda.synchronize()
+                        ts[name].append(e0.elapsed_time(e1) / inner)
+                es = 4 if dtype == torch.float32 else 8
+                lower = lay.p * (lay.p + 64) / 2
+                for name in progs:
+                    ms = statistics.median(ts[name])
+                    rows.append({"case": "LIN", "kernel": name, "n": n, "d": d, "dtype": dtn, "ms": round(ms, 4),
+                                 "ms_min": round(min(ts[name]), 4), "ms_max": round(max(ts[name]), 4),
+                                 "GBps_lower_tiles": round(lower * es / (ms * 1e-3) / 1e9, 1)})
+    finally:
+        nat.tune("asm_f32_fast", old)
+    return rows
+
+
 if __name__ == "__main__":
     for c in sys.argv[1:] or ["C5", "C3", "SE8192"]:
-        print(json.dumps(run(c)), flush=True)
+        if c == "LIN":
+            for row in run_leaves():
+                print(json.dumps(row), flush=True)
+        else:
+            print(json.dumps(run(c)), flush=True)

@@ -8,8 +8,15 @@ Hyperparameters are one flat list in child DFS order, sliced by each child's
 
 ChangePointOperator (Operators.py:370-681) splits the (1-D) input axis at its change points; its
 matrix is the sum of the child matrices masked by the segment indicators, and its hyperparameters
-are the change points followed by the children's.  The segmented LML path does not build that
-matrix at all: SegmentedCovarianceMatrix factors the segments as one ragged device batch.
+are the change points followed by the children's.  Three ways to it:
+  * the device program (``_emit``; everything behind ``engine.kernel_descriptor``: the holistic covariance
+    matrix, -LML, its gradient -- the change points' included, under the SIGMOID / APPROX_INDICATOR masks --
+    the posterior, kernel_vjp): each child is multiplied by a window leaf w_i(x) w_i(y) (GPK_OP_CPW) in ONE
+    launch, 1-D inputs, up to four single-leaf children (GPK_MAX_NODES);
+  * ``get_tf_tensor``: one device launch per child and the masks as torch elementwise ops (any input
+    dimensionality; C + 1 full matrices);
+  * the segmented LML path, which does not build that matrix at all: SegmentedCovarianceMatrix factors the
+    segments as one ragged device batch (exact for the hard INDICATOR mask only).
 """
 from __future__ import annotations
 
@@ -209,8 +216,12 @@ class ChangePointOperator(Operator):
     x < cp_i (ind_{-1} = 0, ind_last = 1) -- the product of the mask outer products that
     get_cp_encapsulated_kernel applies child by child (:410-440).  The indicator follows
     ``global_parameters.p_cp_operator_type``: INDICATOR (default, :397-400), SIGMOID (:387-394) or
-    APPROX_INDICATOR (:379-385).  Every child matrix comes from the device kernel-matrix build; the
-    masks are applied on the device.
+    APPROX_INDICATOR (:379-385).
+
+    Where it runs: ``_emit`` flattens the operator (1-D inputs) into the device program -- a window leaf times each
+    child -- so GaussianProcess / LogLikelihood / predict / kernel_vjp evaluate it, and differentiate it with respect
+    to the change points, inside the same launches as any other tree.  ``get_tf_tensor`` stays the per-child
+    composition: every child matrix from the device kernel-matrix build, the masks applied by torch on the device.
     """
     operator_sign = "]["
 
@@ -222,10 +233,32 @@ class ChangePointOperator(Operator):
         self.sortable = False
 
     def _emit(self, nodes: list, offset: int, ard_slots: list, dim: int) -> int:
+        """``W_0 K_0 MUL  W_1 K_1 MUL ADD ...``: child i's window leaf (GPK_OP_CPW, w_i(x) w_i(y)) BEFORE the child,
+        so the device may skip the child where the window is zero.  Window i reads its one or two bounds from
+        consecutive slots starting at cp_{i-1} (or cp_i for i = 0): adjacent windows share a slot, the flat list stays
+        the reference's [cp_0 .. cp_{C-1}, hyp(K_0), ..].  The mask form is read here, at emission."""
         if len(self.child_nodes) == 1:
             return self.child_nodes[0]._emit(nodes, offset, ard_slots, dim)
-        raise NotImplementedError("a ChangePointOperator is evaluated segment by segment (masked child "
-                                  "matrices / SegmentedCovarianceMatrix), not as one device program")
+        if dim != 1:
+            raise NotImplementedError("the device form of a ChangePointOperator is 1-D (input dimensionality %d): "
+                                      "use get_tf_tensor or the segmented classes" % dim)
+        if not nat.op_supported(nat.OP_CPW):
+            raise nat.NativeUnavailable("libgpk.so has no change-point window leaf (stale build): rebuild it with "
+                                        "__graft_entry__.build()")
+        t = global_param.p_cp_operator_type
+        form = (nat.NODE_CP_SIGMOID if t == global_param.ChangePointOperatorType.SIGMOID else
+                nat.NODE_CP_APPROX if t == global_param.ChangePointOperatorType.APPROX_INDICATOR else 0)
+        ncp = len(self.change_point_positions)
+        child_offset = offset + ncp
+        for i, cn in enumerate(self.child_nodes):
+            lo, hi = i > 0, i < ncp
+            flags = form | (nat.NODE_CP_LO if lo else 0) | (nat.NODE_CP_HI if hi else 0)
+            nodes.append((nat.OP_CPW, offset + (i - 1 if lo else i), -1, flags))
+            child_offset = cn._emit(nodes, child_offset, ard_slots, dim)
+            nodes.append((nat.OP_MUL, 0, -1, 0))
+            if i > 0:
+                nodes.append((nat.OP_ADD, 0, -1, 0))
+        return child_offset
 
     @staticmethod
     def _mask(x: torch.Tensor, cp) -> torch.Tensor:

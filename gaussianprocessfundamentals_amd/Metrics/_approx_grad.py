@@ -42,8 +42,9 @@ class NystroemAdjoint:
         d = int(X.shape[1])
         kd = engine.kernel_descriptor(kernel, d)
         dev = X.device
-        # k(x, x) is the same for every x unless the tree has a LIN leaf (the one non-stationary base kernel)
-        self.stationary = all(kd.nodes[q].op != engine.nat.OP_LIN for q in range(kd.n_nodes))
+        # k(x, x) is the same for every x unless the tree has a LIN leaf or a change-point window leaf
+        # (k(x, x) = sum_i w_i(x)^2 k_i(x, x))
+        self.stationary = all(kd.nodes[q].op not in (engine.nat.OP_LIN, engine.nat.OP_CPW) for q in range(kd.n_nodes))
         self.hyp_bar = torch.zeros(kd.n_hyp, dtype=torch.float64, device=dev)
         self.noise_bar = torch.zeros((), dtype=torch.float64, device=dev)
         self.knm_bar = None
@@ -176,8 +177,8 @@ class NystroemAdjoint:
 
     def diag_adjoint(self) -> torch.Tensor:
         """sum_i d k(x_i, x_i) / d theta, the adjoint of trace(K).  Stationary trees: k(x, x) is the same for every
-        x, so n times one point's.  A tree with a LIN leaf (k(x, x) = sg sum_k (x_k - c_k)^2 depends on x): the
-        kernel's reverse mode with identity weights over chunks of the training points (gpk_kernel_vjp skips the
+        x, so n times one point's.  A tree with a LIN leaf (k(x, x) = sg sum_k (x_k - c_k)^2 depends on x) or a
+        change-point window leaf (k(x, x) = sum_i w_i(x)^2 k_i(x, x)): the kernel's reverse mode with identity weights over chunks of the training points (gpk_kernel_vjp skips the
         zero weights; no n x n matrix)."""
         dev = self.X.device
         if self.stationary:

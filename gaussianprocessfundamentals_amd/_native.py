@@ -17,7 +17,9 @@ from . import _build
 GPK_ABI_VERSION = 7
 GPK_F64, GPK_F32 = 0, 1
 OP_LIN, OP_PER, OP_SE, OP_MAT32, OP_MAT52, OP_ADD, OP_MUL = 102, 104, 105, 107, 108, 201, 202
+OP_CPW = 203  # change-point window leaf w(x) w(y) (the value of KernelManifestation.CP)
 NODE_SCALED, NODE_ARD, NODE_SE_EXPANDED, NODE_STANDARD = 1, 2, 4, 8
+NODE_CP_LO, NODE_CP_HI, NODE_CP_SIGMOID, NODE_CP_APPROX = 16, 32, 64, 128
 MAX_NODES, MAX_DIM, MAX_ARD, MAX_HYP = 16, 16, 2, 64
 NUM_CLASSES = 7
 TIMING_CLASSES = ("assemble", "diag", "trsm", "update", "finalize", "trsv", "grad")
@@ -34,6 +36,7 @@ EXPORTS = (
     "gpk_ski_weights", "gpk_add_diagonal", "gpk_distance_matrix", "gpk_workspace_bytes", "gpk_nlml_batched", "gpk_potrf_lower", "gpk_trsv_lower", "gpk_posterior",
     "gpk_kernel_vjp_workspace_bytes", "gpk_kernel_vjp", "gpk_pinv_backward_scale", "gpk_syevd_workspace_bytes",
     "gpk_syevd", "gpk_chain_plan", "gpk_tune_thread", "gpk_chain_stats", "gpk_chain_plan_ex",
+    "gpk_op_supported",
 )
 
 
@@ -128,8 +131,11 @@ def _declare(lib):
         "gpk_kernel_vjp_workspace_bytes": (c_size_t, [POINTER(GpkKdesc), c_int64, c_int64, c_int32, c_int32]),
         "gpk_kernel_vjp": (c_int, [POINTER(GpkKdesc), P, P, c_int64, P, c_int64, c_int32, P, c_int64, P, P, P, P,
                                    P, c_size_t, P]),
+        "gpk_op_supported": (c_int, [c_int32]),
     }
     for name, (res, args) in sig.items():
+        if name == "gpk_op_supported" and not hasattr(lib, name):
+            continue  # (a library built before the entry existed -- same ABI number: op_supported() then says no)
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -157,6 +163,13 @@ def load_library(path: str = None):
         if path is None:
             _lib = lib
         return lib
+
+
+def op_supported(op: int) -> bool:
+    """Whether the loaded libgpk evaluates kernel-program op ``op`` (gpk_op_supported; host only).  A library built
+    before the entry existed counts as supporting none of the ops added since."""
+    fn = getattr(load_library(), "gpk_op_supported", None)
+    return bool(fn is not None and fn(int(op)) == 1)
 
 
 def lib():

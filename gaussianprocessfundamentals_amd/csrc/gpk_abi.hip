@@ -100,6 +100,17 @@ bool valid_kdesc(const gpk_kdesc* kd, int64_t d) {
       if (nd.hyp_offset < 0 || nd.hyp_offset + need > kd->n_hyp) return false;
       sp += 1;
       if (sp > 8) return false;
+    } else if (nd.op == GPK_OP_CPW) {
+      // change-point window: 1-D inputs, one or two consecutive bounds, one mask form; reads the raw points
+      if (kd->dim != 1) return false;
+      const int nb = ((nd.flags & GPK_NODE_CP_LO) ? 1 : 0) + ((nd.flags & GPK_NODE_CP_HI) ? 1 : 0);
+      if (nb == 0) return false;
+      if ((nd.flags & GPK_NODE_CP_SIGMOID) && (nd.flags & GPK_NODE_CP_APPROX)) return false;
+      if (nd.flags & (GPK_NODE_SCALED | GPK_NODE_ARD | GPK_NODE_SE_EXPANDED | GPK_NODE_STANDARD)) return false;
+      if (nd.ard_slot != -1) return false;
+      if (nd.hyp_offset < 0 || nd.hyp_offset + nb > kd->n_hyp) return false;
+      sp += 1;
+      if (sp > 8) return false;
     } else if (nd.op == GPK_OP_SE || nd.op == GPK_OP_PER || nd.op == GPK_OP_MAT32 ||
                nd.op == GPK_OP_MAT52) {
       const bool ard = (nd.flags & GPK_NODE_ARD) != 0;
@@ -228,6 +239,9 @@ struct Tune {
                           // another) instead of one per 32-row slice (1; 0: per slice; 2 auto: on a grid of at most 2
                           // workgroups per diagonal block -- the CU-share launches side by side -- and for
                           // identity-augmented plans of at least 64 diagonal blocks; N = 6144 within the spread either way)
+  int64_t cp_skip;        // K build of a tree with change-point window leaves: a window that is exactly 0.0 for all of a
+                          // tile's row points or all of its column points skips its MUL sibling there (0: never, A/B;
+                          // equal under == for finite sibling values)
   // (new fields go last: tune() initialises the struct positionally)
 };
 
@@ -259,7 +273,8 @@ Tune& tune() {
                          env_i64("GPK_CHAIN_XCD", 0), env_i64("GPK_CHAIN_XCD_SEATS", 16),
                          env_i64("GPK_ASM_F32_CHUNK", 4), env_i64("GPK_CHAIN_F32", 1),
                          env_i64("GPK_CHAIN_GROUP_NEAR", 2), env_i64("GPK_CHAIN_U128", 2),
-                         env_i64("GPK_CHAIN_NEAR_LA", 1), env_i64("GPK_CHAIN_S128", 2)};
+                         env_i64("GPK_CHAIN_NEAR_LA", 1), env_i64("GPK_CHAIN_S128", 2),
+                         env_i64("GPK_CP_SKIP", 1)};
   return t;
 }
 
@@ -293,7 +308,7 @@ const Knob kKnobs[] = {
     {"chain_xcd_seats", &Tune::chain_xcd_seats}, {"asm_f32_chunk", &Tune::asm_f32_chunk},
     {"chain_f32", &Tune::chain_f32},         {"chain_group_near", &Tune::chain_group_near},
     {"chain_u128", &Tune::chain_u128},         {"chain_near_la", &Tune::chain_near_la},
-    {"chain_s128", &Tune::chain_s128},
+    {"chain_s128", &Tune::chain_s128},       {"cp_skip", &Tune::cp_skip},
 };
 
 int64_t Tune::*knob_field(const char* key) {
@@ -998,11 +1013,22 @@ namespace gpk {
 bool tune_asm_feat() { return tune_now().asm_feat != 0; }
 bool tune_asm_f32_fast() { return tune_now().asm_f32_fast != 0; }
 int tune_asm_f32_chunk() { return (int)std::max<int64_t>(1, std::min<int64_t>(64, tune_now().asm_f32_chunk)); }
+bool tune_cp_skip() { return tune_now().cp_skip != 0; }
 }  // namespace gpk
 
 extern "C" {
 
 int gpk_abi_version(void) { return GPK_ABI_VERSION; }
+
+int gpk_op_supported(int32_t op) {
+  switch (op) {
+    case GPK_OP_LIN: case GPK_OP_PER: case GPK_OP_SE: case GPK_OP_MAT32: case GPK_OP_MAT52:
+    case GPK_OP_ADD: case GPK_OP_MUL: case GPK_OP_CPW:
+      return 1;
+    default:
+      return 0;
+  }
+}
 
 const char* gpk_last_error(void) { return g_err.c_str(); }
 

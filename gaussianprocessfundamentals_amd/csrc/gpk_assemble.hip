@@ -19,6 +19,9 @@
 //   MAT52  KernelBasics/BaseKernels.py:859-880   ((1 + f) + 5 d1^2 / (3 l^2)) e^-f,  f = (sqrt5 d1) / |l|
 //   LIN    KernelBasics/BaseKernels.py:114-134   (x - c)(y - c)^T over the dimensions, c one offset per dimension
 //   ADD/MUL KernelBasics/Operators.py:207-225, :306-326 (left fold over children)
+//   CPW    KernelBasics/Operators.py:379-476      the change-point operator's mask of one child, w(x) w(y) with
+//          w(x) = (1 - ind(x; cp_prev)) ind(x; cp): a leaf that multiplies its child (gpk_kernels.h, cp_window);
+//          staged once per point, and a window that is zero on a whole tile edge skips its child there
 //   d1 = L1 distance (Auxiliary/Distances.py:10-12); SE distance either the expanded norm of
 //   Auxiliary/Distances.py:4-7 (GPK_NODE_SE_EXPANDED) or the direct sum of squares.
 //   noise on the training diagonal only: Statistics/CovarianceMatrix.py:197-206; K_ss has none
@@ -57,11 +60,16 @@ __device__ __forceinline__ int64_t member_m(const AsmArgs& a, int b) { return a.
 
 // Stage 64 points (raw + per-ARD-node rescaled copies) of one tile edge into LDS.  sc_slot > 0: also
 // sin(pi f) and cos(pi f) of u = x / p (f = u - rint(u)) for the periodic node sc_node(kd) into slots
-// sc_slot and sc_slot + 1, clearing *sc_flag if any |u| exceeds SC_MAX_U.
+// sc_slot and sc_slot + 1, clearing *sc_flag if any |u| exceeds SC_MAX_U.  w_slot > 0 (the K build of a program with
+// change-point window leaves, dim 1): the k-th window leaf's w(x) of every point into slot w_slot + k -- once per
+// point and tile edge, so the leaf costs one multiply per element -- and bit q of *cp_nz set if window node q is
+// nonzero at any of the 64 points (padding points stage x = 0, whose w counts too: the skip only gets rarer).
 __device__ __forceinline__ void stage_points(const gpk_kdesc& kd, const AsmArgs& a, const double* hyp,
                                              double* dst, int64_t g0, int b, bool rows, int slot_stride,
-                                             int sc_slot = 0, double sc_iper = 0.0, int* sc_flag = nullptr) {
+                                             int sc_slot = 0, double sc_iper = 0.0, int* sc_flag = nullptr,
+                                             int w_slot = 0, unsigned long long* cp_nz = nullptr) {
   const int tid = threadIdx.x;
+  unsigned long long nz = 0ull;
   for (int e = tid; e < ATILE * a.d; e += 256) {
     const int pt = e / a.d, k = e - pt * a.d;
     const int64_t g = g0 + pt;
@@ -90,7 +98,19 @@ __device__ __forceinline__ void stage_points(const gpk_kdesc& kd, const AsmArgs&
       if (nd.op != GPK_OP_ADD && nd.op != GPK_OP_MUL && (nd.flags & GPK_NODE_ARD))
         dst[(nd.ard_slot + 1) * slot_stride + pt * a.dp + k] = v / hyp[nd.hyp_offset + k];
     }
+    if (w_slot > 0) {
+      int kw = 0;
+      for (int q = 0; q < kd.n_nodes; ++q) {
+        const gpk_node nd = kd.nodes[q];
+        if (nd.op != GPK_OP_CPW) continue;
+        const double w = cp_window(nd.flags, hyp + nd.hyp_offset, v);
+        dst[(w_slot + kw) * slot_stride + pt * a.dp + k] = w;
+        if (w != 0.0) nz |= 1ull << q;
+        ++kw;
+      }
+    }
   }
+  if (w_slot > 0 && nz != 0ull) atomicOr(cp_nz, nz);
 }
 
 #ifndef GPK_ASM_INTERIOR_TREE
@@ -158,7 +178,7 @@ template <typename TOut, int D>
 __device__ __forceinline__ void interior_tree(const gpk_kdesc& kd, const FastNode* fns, const double* prow,
                                               const double* pcol, int off1, int dp, int c, int r0, int64_t gi0,
                                               int64_t gj, double noise, TOut* W, int64_t ld, int sc_sin, int sc_cos,
-                                              bool sc_on) {
+                                              bool sc_on, unsigned cp_zero) {
   double cb0[D], cb1[D], csb[D], ccb[D];
 #pragma unroll
   for (int k = 0; k < D; ++k) {
@@ -178,6 +198,18 @@ __device__ __forceinline__ void interior_tree(const gpk_kdesc& kd, const FastNod
         const double below = st.get(sp - 2);
         st.set(sp - 2, op == GPK_OP_ADD ? below + top : below * top);
         sp -= 1;
+      } else if (op == GPK_OP_CPW) {
+        // window leaf: the product of the two staged w's (eval_tree_fast's value); zero on this tile: +0.0 for
+        // (window, sibling, MUL)
+        const int off = fns[q].off;
+        const int skip_to = __builtin_amdgcn_readfirstlane(fns[q].skip_to);  // (uniform: the program counter stays scalar)
+        if (((cp_zero >> q) & 1u) && skip_to > 0) {
+          st.set(sp, 0.0);
+          q = skip_to;
+        } else {
+          st.set(sp, prow[off + rr * dp] * pcol[off + c * dp]);
+        }
+        sp += 1;
       } else {
         FastNode f = fns[q];
         f.d = D;
@@ -260,7 +292,8 @@ __device__ __forceinline__ void leaf_dispatch(const FastNode& f, bool sc_on, con
     case GPK_OP_MAT32: leaf_rows<D, GPK_OP_MAT32>(f, prow, pcol, dp, c, r0, mode, acc); break;
     case GPK_OP_MAT52: leaf_rows<D, GPK_OP_MAT52>(f, prow, pcol, dp, c, r0, mode, acc); break;
     case GPK_OP_LIN: leaf_rows<D, GPK_OP_LIN>(f, prow, pcol, dp, c, r0, mode, acc); break;
-    default:  // (no such leaf passes valid_kdesc; were one to, NaN rather than another op's formula)
+    default:  // (no such leaf passes valid_kdesc -- a program with a window leaf, GPK_OP_CPW, never takes this two-leaf
+              // path, launch_assemble; were one to, NaN rather than another op's formula)
 #pragma unroll
       for (int i = 0; i < ATILE / 4; ++i) acc[i] = NAN;
       break;
@@ -526,7 +559,7 @@ template <typename TOut, int D, int TREE>
 __device__ __forceinline__ bool interior_d(const gpk_kdesc& kd, const FastNode& fn, const FastNode* fns, bool fast,
                                            const double* prow, const double* pcol, int slot_stride, int dp, int c,
                                            int r0, int64_t gi0, int64_t gj, double noise, TOut* W, int64_t ld,
-                                           int sc_sin, int sc_cos, bool sc_on) {
+                                           int sc_sin, int sc_cos, bool sc_on, int nw, unsigned cp_zero) {
   if (fast) {
     if (sc_on && fn.sc && fn.op == GPK_OP_PER) {
       interior_single_sc<TOut, D>(fn, prow, pcol, dp, c, r0, gi0, gj, noise, W, ld);
@@ -545,8 +578,11 @@ __device__ __forceinline__ bool interior_d(const gpk_kdesc& kd, const FastNode& 
     interior_pair<TOut, D>(kd, fns, prow, pcol, dp, c, r0, gi0, gj, noise, W, ld, sc_on);
     return true;
   }
-  if (!TREE || GPK_ASM_INTERIOR_TREE == 0 || kd.n_ard > 1 || kd.n_nodes > 8) return false;
-  interior_tree<TOut, D>(kd, fns, prow, pcol, slot_stride, dp, c, r0, gi0, gj, noise, W, ld, sc_sin, sc_cos, sc_on);
+  // (programs of more than 8 nodes keep the generic loop -- except change-point trees, 7 / 11 / 15 nodes for two to
+  // four single-leaf children, most of whose nodes the interior loop skips on most tiles)
+  if (!TREE || GPK_ASM_INTERIOR_TREE == 0 || kd.n_ard > 1 || (kd.n_nodes > 8 && nw == 0)) return false;
+  interior_tree<TOut, D>(kd, fns, prow, pcol, slot_stride, dp, c, r0, gi0, gj, noise, W, ld, sc_sin, sc_cos, sc_on,
+                         cp_zero);
   return true;
 }
 
@@ -966,7 +1002,12 @@ __device__ __forceinline__ void assemble_tile(const gpk_kdesc& kd, const AsmArgs
   // slots per tile edge: raw points, one per ARD node, and (periodic node through sin / cos) sin, cos
   const int scq = a.A == nullptr ? sc_node(kd) : -1;
   const int sc_slot = 1 + kd.n_ard;
-  const int nslot = sc_slot + (scq >= 0 ? 2 : 0);
+  // (window leaves: a program with one takes the general tree instantiation whatever its size, launch_assemble; the
+  // other instantiations compile none of the window code, so their registers and occupancy stay what they were)
+  constexpr bool WIN = TREE == 1;
+  const int nw = WIN && a.A == nullptr ? cp_windows(kd) : 0;
+  const int w_slot = sc_slot + (scq >= 0 ? 2 : 0);       // one more slot per window leaf: its staged w(x)
+  const int nslot = w_slot + nw;
   double* hyp_s = smem;                                  // GPK_MAX_HYP
   double* prow = smem + GPK_MAX_HYP;                     // nslot * slot_stride
   double* pcol = prow + nslot * slot_stride;
@@ -982,11 +1023,17 @@ __device__ __forceinline__ void assemble_tile(const gpk_kdesc& kd, const AsmArgs
   // registers below)
   FastNode* fns = reinterpret_cast<FastNode*>(pcol + nslot * slot_stride);
   const int sc_sin = sc_slot * slot_stride, sc_cos = (sc_slot + 1) * slot_stride;
-  if (kd.n_nodes > 1 && tid < kd.n_nodes) {
+  if ((kd.n_nodes > 1 || nw > 0) && tid < kd.n_nodes) {
     const gpk_node nd = kd.nodes[tid];
     if (nd.op != GPK_OP_ADD && nd.op != GPK_OP_MUL) {
       FastNode f = make_fast_node(nd, hyp_s, a.d);
       f.off = (nd.flags & GPK_NODE_ARD) ? (nd.ard_slot + 1) * slot_stride : 0;
+      if (nd.op == GPK_OP_CPW && nw > 0) {
+        int kw = 0;  // its rank among the window leaves: the slot stage_points fills for it
+        for (int q = 0; q < tid; ++q) kw += kd.nodes[q].op == GPK_OP_CPW ? 1 : 0;
+        f.off = (w_slot + kw) * slot_stride;
+        f.skip_to = a.cp_skip ? cp_skip_to(kd, tid) : 0;
+      }
       if (tid == scq) {
         f.sc = 1;
         f.sc_sin = sc_sin;
@@ -998,12 +1045,20 @@ __device__ __forceinline__ void assemble_tile(const gpk_kdesc& kd, const AsmArgs
   const int64_t gi0 = ti * ATILE, gj0 = tj * ATILE;
   if (a.A == nullptr) {
     const double sc_iper = scq >= 0 ? 1.0 / hyp_s[kd.nodes[scq].hyp_offset + 1] : 0.0;
-    stage_points(kd, a, hyp_s, prow, gi0, b, true, slot_stride, scq >= 0 ? sc_slot : 0, sc_iper, &sc_flag);
-    stage_points(kd, a, hyp_s, pcol, gj0, b, false, slot_stride, scq >= 0 ? sc_slot : 0, sc_iper, &sc_flag);
+    // (window leaves: which of them are nonzero anywhere on the tile's rows / columns, as bit masks in pair_max[0] /
+    // pair_max[1] -- zeroed above; their other user, the two-leaf MFMA path, has no window leaves)
+    stage_points(kd, a, hyp_s, prow, gi0, b, true, slot_stride, scq >= 0 ? sc_slot : 0, sc_iper, &sc_flag,
+                 nw > 0 ? w_slot : 0, &pair_max[0]);
+    stage_points(kd, a, hyp_s, pcol, gj0, b, false, slot_stride, scq >= 0 ? sc_slot : 0, sc_iper, &sc_flag,
+                 nw > 0 ? w_slot : 0, &pair_max[1]);
   }
   __syncthreads();
   // the sin / cos form for this tile: every staged point within |x / p| <= SC_MAX_U (workgroup-uniform)
   const bool sc_on = scq >= 0 && sc_flag != 0;
+  // window leaves that are exactly zero for all of the tile's row points or all of its column points
+  // (workgroup-uniform: read after the barrier; only nodes with a skip_to act on it)
+  const unsigned cp_zero =
+      nw > 0 ? (unsigned)__builtin_amdgcn_readfirstlane((int)~(unsigned)(pair_max[0] & pair_max[1])) : 0u;
   if (TREE == 3 && sc_on && a.A == nullptr && a.d >= 4 && !GPK_ASM_ABLATE) {
     // two-leaf SE + periodic tree: the tile on f64 MFMA (pair_mfma_tile) when its error bounds hold
     const gpk_node n0 = kd.nodes[0], n1 = kd.nodes[1];
@@ -1053,7 +1108,7 @@ __device__ __forceinline__ void assemble_tile(const gpk_kdesc& kd, const AsmArgs
       if (gi >= a.n || gj >= a.m) continue;
       if (a.uplo && gj > gi) continue;
       double v;
-      if (kd.n_nodes == 1) {
+      if (kd.n_nodes == 1 && nw == 0) {
         FastNode f1 = make_fast_node(kd.nodes[0], hyp_s, a.d);
         f1.sc = scq == 0 ? 1 : 0;
         f1.sc_sin = sc_sin;
@@ -1061,7 +1116,7 @@ __device__ __forceinline__ void assemble_tile(const gpk_kdesc& kd, const AsmArgs
         v = fast_value(f1, prow + rr * a.dp + fast_off(kd, slot_stride), pcol + c * a.dp + fast_off(kd, slot_stride),
                        sc_on);
       } else {
-        v = eval_tree_fast(kd, fns, prow + rr * a.dp, pcol + c * a.dp, sc_on);
+        v = eval_tree_fast<WIN>(kd, fns, prow + rr * a.dp, pcol + c * a.dp, sc_on, cp_zero);
       }
       if (gi == gj) v += a.diag_add;
       W[gi * a.ld + gj] = (TOut)v;
@@ -1073,7 +1128,7 @@ __device__ __forceinline__ void assemble_tile(const gpk_kdesc& kd, const AsmArgs
   const int ccls = classify(a, gj, nm, mm);
   const double yv = (ccls == CLS_TRAIN) ? a.y[(int64_t)b * a.y_bs + gj] : 0.0;
   const bool col_kernel = (ccls == CLS_TRAIN || ccls == CLS_TEST);
-  const bool fast = kd.n_nodes == 1;
+  const bool fast = kd.n_nodes == 1 && nw == 0;
   FastNode fn = make_fast_node(kd.nodes[0], hyp_s, a.d);
   fn.off = fast_off(kd, slot_stride);
   fn.sc = scq == 0 ? 1 : 0;
@@ -1082,11 +1137,11 @@ __device__ __forceinline__ void assemble_tile(const gpk_kdesc& kd, const AsmArgs
   if (TREE != 3 && GPK_ASM_INTERIOR && !a.generic && a.A == nullptr && gi0 + ATILE <= nm) {  // lower tiles: gj0 <= gi0
     bool done = false;
     switch (a.d) {
-      case 1: done = interior_d<TOut, 1, TREE>(kd, fn, fns, fast, prow, pcol, slot_stride, a.dp, c, r0, gi0, gj, noise, W, a.ld, sc_sin, sc_cos, sc_on); break;
-      case 2: done = interior_d<TOut, 2, TREE>(kd, fn, fns, fast, prow, pcol, slot_stride, a.dp, c, r0, gi0, gj, noise, W, a.ld, sc_sin, sc_cos, sc_on); break;
-      case 3: done = interior_d<TOut, 3, TREE>(kd, fn, fns, fast, prow, pcol, slot_stride, a.dp, c, r0, gi0, gj, noise, W, a.ld, sc_sin, sc_cos, sc_on); break;
-      case 4: done = interior_d<TOut, 4, TREE>(kd, fn, fns, fast, prow, pcol, slot_stride, a.dp, c, r0, gi0, gj, noise, W, a.ld, sc_sin, sc_cos, sc_on); break;
-      case 8: done = interior_d<TOut, 8, TREE>(kd, fn, fns, fast, prow, pcol, slot_stride, a.dp, c, r0, gi0, gj, noise, W, a.ld, sc_sin, sc_cos, sc_on); break;
+      case 1: done = interior_d<TOut, 1, TREE>(kd, fn, fns, fast, prow, pcol, slot_stride, a.dp, c, r0, gi0, gj, noise, W, a.ld, sc_sin, sc_cos, sc_on, nw, cp_zero); break;
+      case 2: done = interior_d<TOut, 2, TREE>(kd, fn, fns, fast, prow, pcol, slot_stride, a.dp, c, r0, gi0, gj, noise, W, a.ld, sc_sin, sc_cos, sc_on, nw, cp_zero); break;
+      case 3: done = interior_d<TOut, 3, TREE>(kd, fn, fns, fast, prow, pcol, slot_stride, a.dp, c, r0, gi0, gj, noise, W, a.ld, sc_sin, sc_cos, sc_on, nw, cp_zero); break;
+      case 4: done = interior_d<TOut, 4, TREE>(kd, fn, fns, fast, prow, pcol, slot_stride, a.dp, c, r0, gi0, gj, noise, W, a.ld, sc_sin, sc_cos, sc_on, nw, cp_zero); break;
+      case 8: done = interior_d<TOut, 8, TREE>(kd, fn, fns, fast, prow, pcol, slot_stride, a.dp, c, r0, gi0, gj, noise, W, a.ld, sc_sin, sc_cos, sc_on, nw, cp_zero); break;
       default: break;
     }
     if (done) return;
@@ -1113,7 +1168,7 @@ __device__ __forceinline__ void assemble_tile(const gpk_kdesc& kd, const AsmArgs
     } else if ((rcls == CLS_TRAIN || rcls == CLS_TEST) && col_kernel) {
       if (!GPK_ASM_ABLATE)
         v = fast ? fast_value(fn, prow + fn.off + rr * a.dp, pcol + fn.off + c * a.dp, sc_on)
-                 : eval_tree_fast(kd, fns, prow + rr * a.dp, pcol + c * a.dp, sc_on);
+                 : eval_tree_fast<WIN>(kd, fns, prow + rr * a.dp, pcol + c * a.dp, sc_on, cp_zero);
       if (rcls == CLS_TRAIN && ccls == CLS_TRAIN && gi == gj) v += noise;
     } else if (rcls == CLS_Y && ccls == CLS_TRAIN) {
       v = yv;
@@ -1251,6 +1306,17 @@ __device__ __forceinline__ void base_partials(const gpk_node& nd, const double* 
         acc[k] -= coef * sg * (ta + tb);
       }
     if (scaled) acc[GPK_MAX_DIM] += coef * s;
+    return;
+  }
+  if (nd.op == GPK_OP_CPW) {
+    // k = w(a) w(b): d k / d cp = w'(a) w(b) + w(a) w'(b) for each bound the leaf has (acc[0], acc[1]); the hard
+    // mask has no derivative (cp_ind_dcp)
+    const double wa = cp_window(fl, h, a[0]), wb = cp_window(fl, h, b[0]);
+    double da[2], db[2];
+    cp_window_dcp(fl, h, a[0], da);
+    cp_window_dcp(fl, h, b[0], db);
+    acc[0] += coef * (da[0] * wb + wa * db[0]);
+    acc[1] += coef * (da[1] * wb + wa * db[1]);
     return;
   }
   if (nd.op == GPK_OP_PER) {
@@ -1407,7 +1473,8 @@ __global__ __launch_bounds__(256) void grad_kernel(gpk_kdesc kd, AsmArgs a, Grad
     // hyperparameter slots of this node: ARD l_0..l_{d-1} then sg (stored at acc[GPK_MAX_DIM])
     const bool ard = (nd.flags & GPK_NODE_ARD) != 0;
     const bool vec = ard || nd.op == GPK_OP_LIN;  // d vector entries (ARD l, LIN c), then sg
-    const int nshape = vec ? a.d : (nd.op == GPK_OP_PER ? 2 : 1);
+    const bool win = nd.op == GPK_OP_CPW;         // its one or two bounds, no sg
+    const int nshape = win ? cp_bounds(nd.flags) : vec ? a.d : (nd.op == GPK_OP_PER ? 2 : 1);
     const bool scaled = (nd.flags & GPK_NODE_SCALED) != 0;
     const bool sg_moved = vec && scaled;
     const int np = nshape + (scaled ? 1 : 0);
@@ -1419,9 +1486,19 @@ __global__ __launch_bounds__(256) void grad_kernel(gpk_kdesc kd, AsmArgs a, Grad
       }
     }
     __syncthreads();
-    if (tid < np)
+    if (win) {
+      // adjacent window leaves share a bound's slot (cp_i: upper bound of window i, lower bound of window i + 1): the
+      // later leaf adds to what the earlier one wrote.  Thread s owns slot s for every window leaf, so the sum is
+      // that thread's own read-modify-write in program order (deterministic)
+      const int k = tid - nd.hyp_offset;
+      if (k >= 0 && k < np) {
+        const double sres = red[k] + red[(GNP + 1) + k] + red[2 * (GNP + 1) + k] + red[3 * (GNP + 1) + k];
+        part[tid] = cp_slot_written(kd, qn, tid) ? part[tid] + sres : sres;
+      }
+    } else if (tid < np) {
       part[nd.hyp_offset + tid] = red[tid] + red[(GNP + 1) + tid] + red[2 * (GNP + 1) + tid] +
                                   red[3 * (GNP + 1) + tid];
+    }
     __syncthreads();
   }
   const double ns = wave_sum(noise_acc);
@@ -1470,6 +1547,12 @@ __device__ __forceinline__ void base_input_partials(const gpk_node& nd, const do
 #pragma unroll
     for (int k = 0; k < GPK_MAX_DIM; ++k)
       if (k < d) acc[k] += coef * sg * (a[k] - h[k]);
+    return;
+  }
+  if (nd.op == GPK_OP_CPW) {  // d (w(a) w(b)) / d b = w(a) w'(b), w'(x) = -(d w / d cp_lo + d w / d cp_hi); dimension 0
+    double db[2];
+    cp_window_dcp(fl, h, b[0], db);
+    acc[0] -= coef * cp_window(fl, h, a[0]) * (db[0] + db[1]);
     return;
   }
   const double v = base_value(nd, hyp, a, b, d);  // includes sg
@@ -1598,7 +1681,8 @@ __global__ __launch_bounds__(256) void vjp_kernel(gpk_kdesc kd, AsmArgs a, VjpAr
     for (int k = 0; k < GPK_MAX_DIM; ++k)
       if (k < a.d) gz[k] += ard ? az[k] / hyp_s[nd.hyp_offset + k] : az[k];
     const bool vec = ard || nd.op == GPK_OP_LIN;  // d vector entries (ARD l, LIN c), then sg
-    const int nshape = vec ? a.d : (nd.op == GPK_OP_PER ? 2 : 1);
+    const bool win = nd.op == GPK_OP_CPW;         // its one or two bounds, no sg
+    const int nshape = win ? cp_bounds(nd.flags) : vec ? a.d : (nd.op == GPK_OP_PER ? 2 : 1);
     const bool scaled = (nd.flags & GPK_NODE_SCALED) != 0;
     const bool sg_moved = vec && scaled;
     const int np = nshape + (scaled ? 1 : 0);
@@ -1610,7 +1694,16 @@ __global__ __launch_bounds__(256) void vjp_kernel(gpk_kdesc kd, AsmArgs a, VjpAr
       }
     }
     __syncthreads();
-    if (tid < np) part[nd.hyp_offset + tid] = red[tid] + red[GNP + tid] + red[2 * GNP + tid] + red[3 * GNP + tid];
+    if (win) {
+      // a bound shared with an earlier window leaf: add (thread s owns slot s, as in grad_kernel)
+      const int k = tid - nd.hyp_offset;
+      if (k >= 0 && k < np) {
+        const double sres = red[k] + red[GNP + k] + red[2 * GNP + k] + red[3 * GNP + k];
+        part[tid] = cp_slot_written(kd, qn, tid) ? part[tid] + sres : sres;
+      }
+    } else if (tid < np) {
+      part[nd.hyp_offset + tid] = red[tid] + red[GNP + tid] + red[2 * GNP + tid] + red[3 * GNP + tid];
+    }
     __syncthreads();
   }
   if (!g.want_z) return;
@@ -1767,9 +1860,14 @@ static bool tune_pair_off() {  // GPK_ASM_PAIR=0: two-leaf trees through the gen
   return off;
 }
 
-hipError_t launch_assemble(const gpk_kdesc& kd, const AsmArgs& a, int dtype, int32_t batch,
+hipError_t launch_assemble(const gpk_kdesc& kd, const AsmArgs& a_in, int dtype, int32_t batch,
                            hipStream_t s) {
-  const int nslot = 1 + kd.n_ard + ((a.A == nullptr && sc_node(kd) >= 0) ? 2 : 0);
+  AsmArgs a = a_in;
+  a.cp_skip = tune_cp_skip() ? 1 : 0;
+  // point slots per tile edge: raw, one per ARD node, the periodic node's sin / cos, one per change-point window leaf
+  // (its staged w: n_windows x 64 x 8 bytes per edge at dim 1; none for a program without windows)
+  const int nw = a.A == nullptr ? cp_windows(kd) : 0;
+  const int nslot = 1 + kd.n_ard + ((a.A == nullptr && sc_node(kd) >= 0) ? 2 : 0) + nw;
   const size_t lds = sizeof(double) * (GPK_MAX_HYP + 2 * (size_t)nslot * ATILE * a.dp) +
                      sizeof(FastNode) * GPK_MAX_NODES + sizeof(double) * (2 * ATILE + 32);  // (+ pair_mfma_tile's)
   dim3 grid;
@@ -1785,7 +1883,9 @@ hipError_t launch_assemble(const gpk_kdesc& kd, const AsmArgs& a, int dtype, int
   // instantiation: 0 single base node, 2 two leaves under one ADD / MUL, 3 the two leaves SE (direct norm) and a
   // separable periodic node at D >= 4 (pair_mfma_tile), 1 any other tree
   const bool pair = kd.n_nodes == 3 && (kd.nodes[2].op == GPK_OP_ADD || kd.nodes[2].op == GPK_OP_MUL);
-  int tree = kd.n_nodes == 1 ? 0 : (pair && !tune_pair_off() ? 2 : 1);
+  // (a window leaf is evaluated by the general tree instantiation only: a program with one takes tree 1 whatever its
+  // size -- a change-point tree has at least 7 nodes anyway)
+  int tree = (kd.n_nodes == 1 && nw == 0) ? 0 : (pair && nw == 0 && !tune_pair_off() ? 2 : 1);
   if (tree == 2 && GPK_ASM_PAIR_MFMA && a.A == nullptr && a.d % 4 == 0 && dtype == GPK_F64) {
     const int q = sc_node(kd);
     const gpk_node se = kd.nodes[q == 0 ? 1 : 0];

@@ -82,6 +82,9 @@ struct AsmArgs {
   // set by launch_assemble only: tiles the MFMA fast kernel left (count, then (member, ti, tj) triples); the
   // general instantiation then loops over this list instead of the grid
   const int32_t* tlist;
+  // set by launch_assemble only: gpk_tune("cp_skip") -- a change-point window leaf that is exactly zero on a whole
+  // tile edge skips its MUL sibling on that tile
+  int32_t cp_skip;
 };
 
 struct GemmArgs {
@@ -261,6 +264,7 @@ struct TrsvArgs {
 bool tune_asm_feat();  // gpk_tune("asm_feat") in effect on this thread
 bool tune_asm_f32_fast();  // gpk_tune("asm_f32_fast") in effect on this thread
 int tune_asm_f32_chunk();  // gpk_tune("asm_f32_chunk"), clamped to 1 .. 64
+bool tune_cp_skip();       // gpk_tune("cp_skip") in effect on this thread
 hipError_t launch_assemble(const gpk_kdesc& kd, const AsmArgs& a, int dtype, int32_t batch,
                            hipStream_t s);
 hipError_t launch_diag(const DiagArgs& a, int dtype, int32_t batch, hipStream_t s);

@@ -16,6 +16,101 @@ constexpr double SQRT3 = 1.7320508075688772;
 constexpr double SQRT5 = 2.23606797749979;
 constexpr double PI = 3.141592653589793;
 
+// ------------------------------------------------------------------ change-point window leaf (GPK_OP_CPW)
+// ChangePointOperator's masks (KernelBasics/Operators.py:379-408) on 1-D inputs.  ONE function with one operation
+// order computes a point's window everywhere (the K build stages it once per point and tile edge, the gradient
+// kernels call it per element), so every path multiplies the same two doubles.
+//   INDICATOR         [x < cp]                              d / d cp: 0 (tf.less passes no gradient)
+//   SIGMOID           0.5 (1 + tanh((cp - x) / 0.0025))     d / d cp: 200 sech^2((cp - x) / 0.0025)
+//   APPROX_INDICATOR  1 / (1 + exp(-100 (x - cp)))          d / d cp: -100 s (1 - s)        (rises with x, as upstream)
+// The hard mask is exactly 0.0 / 1.0; the SIGMOID one is exactly 0.0 / 1.0 wherever tanh has rounded to -1 / +1
+// (|cp - x| >~ 0.048): such points make a window exactly +0.0, which the tile-level child skip relies on.
+constexpr double CP_SIGMOID_WIDTH = 0.0025;
+constexpr double CP_APPROX_SLOPE = 100.0;
+
+__device__ __forceinline__ double cp_ind(int fl, double x, double cp) {
+#pragma clang fp contract(on)
+  if (fl & GPK_NODE_CP_SIGMOID) return 0.5 * (1.0 + tanh((cp - x) / CP_SIGMOID_WIDTH));
+  if (fl & GPK_NODE_CP_APPROX) return 1.0 / (1.0 + exp(-CP_APPROX_SLOPE * (x - cp)));
+  return x < cp ? 1.0 : 0.0;
+}
+
+// d ind / d cp (= -d ind / d x)
+__device__ __forceinline__ double cp_ind_dcp(int fl, double x, double cp) {
+#pragma clang fp contract(on)
+  if (fl & GPK_NODE_CP_SIGMOID) {
+    const double ch = cosh((cp - x) / CP_SIGMOID_WIDTH);  // (overflows to inf far from cp: the derivative is 0 there)
+    return (0.5 / CP_SIGMOID_WIDTH) / (ch * ch);
+  }
+  if (fl & GPK_NODE_CP_APPROX) {
+    const double sv = 1.0 / (1.0 + exp(-CP_APPROX_SLOPE * (x - cp)));
+    return -CP_APPROX_SLOPE * (sv * (1.0 - sv));
+  }
+  return 0.0;
+}
+
+__host__ __device__ inline int cp_bounds(int fl) {
+  return ((fl & GPK_NODE_CP_LO) ? 1 : 0) + ((fl & GPK_NODE_CP_HI) ? 1 : 0);
+}
+
+// w(x) = (1 - ind(x; h[0])) [CP_LO] * ind(x; h[lo ? 1 : 0]) [CP_HI]: the reference's previous-complement times this
+// change point's indicator (:414-417, :431-436)
+__device__ __forceinline__ double cp_window(int fl, const double* h, double x) {
+#pragma clang fp contract(on)
+  const bool lo = (fl & GPK_NODE_CP_LO) != 0, hi = (fl & GPK_NODE_CP_HI) != 0;
+  const double wl = lo ? 1.0 - cp_ind(fl, x, h[0]) : 1.0;
+  return hi ? (lo ? wl * cp_ind(fl, x, h[1]) : cp_ind(fl, x, h[0])) : wl;
+}
+
+// d w(x) / d (h[0], h[1]) into dw[0 .. bounds); d w / d x is minus their sum
+__device__ __forceinline__ void cp_window_dcp(int fl, const double* h, double x, double (&dw)[2]) {
+#pragma clang fp contract(on)
+  const bool lo = (fl & GPK_NODE_CP_LO) != 0, hi = (fl & GPK_NODE_CP_HI) != 0;
+  dw[0] = dw[1] = 0.0;
+  if (lo && hi) {
+    dw[0] = -cp_ind_dcp(fl, x, h[0]) * cp_ind(fl, x, h[1]);
+    dw[1] = (1.0 - cp_ind(fl, x, h[0])) * cp_ind_dcp(fl, x, h[1]);
+  } else if (lo) {
+    dw[0] = -cp_ind_dcp(fl, x, h[0]);
+  } else if (hi) {
+    dw[0] = cp_ind_dcp(fl, x, h[0]);
+  }
+}
+
+// whether a window leaf BEFORE node qn reads hyperparameter slot s (adjacent windows share a bound): the gradient
+// reductions then add node qn's partial sum to the slot instead of assigning it
+__host__ __device__ inline bool cp_slot_written(const gpk_kdesc& kd, int qn, int s) {
+  for (int q = 0; q < qn; ++q) {
+    const gpk_node nd = kd.nodes[q];
+    if (nd.op == GPK_OP_CPW && s >= nd.hyp_offset && s < nd.hyp_offset + cp_bounds(nd.flags)) return true;
+  }
+  return false;
+}
+
+// number of window leaves of a program
+__host__ __device__ inline int cp_windows(const gpk_kdesc& kd) {
+  int nw = 0;
+  for (int q = 0; q < kd.n_nodes; ++q) nw += kd.nodes[q].op == GPK_OP_CPW ? 1 : 0;
+  return nw;
+}
+
+// A window leaf directly left of its sibling under a MUL (postfix W <sibling subtree> MUL, what ChangePointOperator
+// emits): the index of that MUL, 0 if the op that consumes the window is not a MUL.  Where the window is zero the
+// evaluator pushes +0.0 and continues after that index.
+__host__ __device__ inline int cp_skip_to(const gpk_kdesc& kd, int q) {
+  int depth = 1;  // stack entries from the window's upwards
+  for (int j = q + 1; j < kd.n_nodes; ++j) {
+    const int op = kd.nodes[j].op;
+    if (op == GPK_OP_ADD || op == GPK_OP_MUL) {
+      // the first op that reaches down to the window's entry consumes it (as the left operand iff depth 2 -> 1)
+      if (--depth <= 1) return (depth == 1 && op == GPK_OP_MUL) ? j : 0;
+    } else {
+      ++depth;
+    }
+  }
+  return 0;
+}
+
 // Values of one base node for R row points a[i] against one column point b.  The R evaluations
 // are independent, so the compiler interleaves their long f64 chains (exp / sin / sqrt / div).
 template <int R>
@@ -92,6 +187,11 @@ __device__ __forceinline__ void base_values(const gpk_node& nd, const double* __
       for (int i = 0; i < R; ++i) r[i] += (a[i][k] - ck) * tb;
     }
     sg_at = d;
+  } else if (nd.op == GPK_OP_CPW) {  // w(a) w(b): the direct form (the K build multiplies the staged w's: same bits)
+    const double wb = cp_window(fl, h, b[0]);
+#pragma unroll
+    for (int i = 0; i < R; ++i) r[i] = cp_window(fl, h, a[i][0]) * wb;
+    return;  // (no sg)
   } else {  // MAT32 / MAT52
     double dist[R];
 #pragma unroll
@@ -176,7 +276,11 @@ struct FastNode {
   // periodic node through the staged sin / cos of its points (sc_node): sin(pi u), cos(pi u) per point and
   // dimension at offsets sc_sin / sc_cos from the point (tiles whose points all have |u| = |x / p| <= 4)
   int sc, sc_sin, sc_cos;
+  // window leaf (GPK_OP_CPW): `off` is the point slot that holds its staged w; skip_to > 0: the MUL that closes
+  // (window, sibling) -- on a tile where the window is zero the evaluator continues after it (cp_skip_to)
+  int skip_to;
 };
+static_assert(sizeof(FastNode) == 80, "the K build's LDS request counts GPK_MAX_NODES of these");
 
 // The periodic node whose sin^2(pi (x_k - y_k) / p) terms the K build takes from per-point sin / cos
 // (sin(a - b) = sin a cos b - cos a sin b; separable per dimension: the standard form, or D = 1 where the
@@ -211,7 +315,7 @@ __device__ __forceinline__ FastNode make_fast_node(const gpk_node& nd, const dou
     f.c = h;
     f.iper = 0.0;
     sg_at = d;
-  } else {
+  } else {  // (a window leaf, GPK_OP_CPW, lands here too: it uses none of these constants)
     l = ard ? 1.0 : (nd.op == GPK_OP_SE ? h[0] : fabs(h[0]));
     f.iper = 0.0;
     sg_at = ard ? d : 1;
@@ -222,6 +326,7 @@ __device__ __forceinline__ FastNode make_fast_node(const gpk_node& nd, const dou
   f.sg = (nd.flags & GPK_NODE_SCALED) ? h[sg_at] : 1.0;
   f.sc = 0;
   f.sc_sin = f.sc_cos = 0;
+  f.skip_to = 0;
   return f;
 }
 
@@ -350,9 +455,13 @@ __device__ __forceinline__ double fast_value(const FastNode& f, const double* a,
 
 // The postfix program with every base node's constants precomputed (fns[q] = make_fast_node of
 // node q, fns[q].off its ARD slot offset): the tree form of the single-node fast path -- no division
-// by a hyperparameter per element, the periodic nodes through sin2_pi.
+// by a hyperparameter per element, the periodic nodes through sin2_pi.  WIN (the instantiation for programs with
+// change-point window leaves; the others carry none of this code): a window leaf's value is the product of its two
+// staged w's (the point slot fns[q].off) -- one multiply per element; cp_zero: bit q set -- window leaf q is exactly
+// zero on this tile (workgroup-uniform): +0.0 stands for (window, sibling, MUL) where the node has a skip_to.
+template <bool WIN = false>
 __device__ __forceinline__ double eval_tree_fast(const gpk_kdesc& kd, const FastNode* fns, const double* pa,
-                                                 const double* pb, bool sc_on = false) {
+                                                 const double* pb, bool sc_on = false, unsigned cp_zero = 0u) {
   Stack st;
   st.s0 = 0.0;
   int sp = 0;
@@ -363,6 +472,17 @@ __device__ __forceinline__ double eval_tree_fast(const gpk_kdesc& kd, const Fast
       const double below = st.get(sp - 2);
       st.set(sp - 2, op == GPK_OP_ADD ? below + top : below * top);
       sp -= 1;
+    } else if (WIN && op == GPK_OP_CPW) {
+      const int off = fns[q].off;
+      // (read as a scalar, so the program counter stays wave-uniform)
+      const int skip_to = __builtin_amdgcn_readfirstlane(fns[q].skip_to);
+      if (((cp_zero >> q) & 1u) && skip_to > 0) {
+        st.set(sp, 0.0);
+        q = skip_to;  // (the loop's increment steps past the MUL)
+      } else {
+        st.set(sp, pa[off] * pb[off]);
+      }
+      sp += 1;
     } else {
       const FastNode f = fns[q];
       st.set(sp, fast_value(f, pa + f.off, pb + f.off, sc_on));

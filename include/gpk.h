@@ -73,7 +73,18 @@ enum {
   GPK_OP_MAT32 = 107,
   GPK_OP_MAT52 = 108,
   GPK_OP_ADD = 201, /* binary: pops two, pushes sum (left fold of an n-ary ADD) */
-  GPK_OP_MUL = 202  /* binary: pops two, pushes product                         */
+  GPK_OP_MUL = 202, /* binary: pops two, pushes product                         */
+  GPK_OP_CPW = 203  /* leaf: the change-point window w(x) w(y) of ChangePointOperator (KernelBasics/Operators.py:
+                       410-476; the value of KernelManifestation.CP), dim 1 only:
+                         w(x) = (1 - ind(x; h[0]))  [GPK_NODE_CP_LO]  *  ind(x; h[lo ? 1 : 0])  [GPK_NODE_CP_HI]
+                       ind: [x < cp], or 0.5 (1 + tanh((cp - x) / 0.0025)) with GPK_NODE_CP_SIGMOID, or
+                       1 / (1 + exp(-100 (x - cp))) with GPK_NODE_CP_APPROX.  hyp_offset: the first bound it reads (its
+                       one or two bounds are consecutive; adjacent windows of one operator share a slot, and the
+                       gradient entries of a shared slot are summed).  A change-point tree is
+                       W_0 K_0 MUL  W_1 K_1 MUL ADD ...: a window directly left of its sibling under a MUL lets the K
+                       build skip the sibling on tiles where the window is exactly zero (gpk_tune "cp_skip").
+                       flags: at least one of CP_LO / CP_HI, at most one of CP_SIGMOID / CP_APPROX, none of
+                       SCALED / ARD / SE_EXPANDED / STANDARD; ard_slot -1 */
 };
 
 /* per-node flags of a base-kernel node */
@@ -81,8 +92,13 @@ enum {
   GPK_NODE_SCALED = 1,     /* p_scaled_base_kernel: signal variance sg multiplies the kernel */
   GPK_NODE_ARD = 2,        /* build extension: one length scale per input dimension          */
   GPK_NODE_SE_EXPANDED = 4, /* SE distance by the reference's expanded norm (Distances.py:5-7) */
-  GPK_NODE_STANDARD = 8     /* MAT: Euclidean distance; PER: sum_d sin^2 per dimension (build
+  GPK_NODE_STANDARD = 8,    /* MAT: Euclidean distance; PER: sum_d sin^2 per dimension (build
                                option; equal to the reference's L1 forms when d == 1)          */
+  /* GPK_OP_CPW nodes only */
+  GPK_NODE_CP_LO = 16,      /* the factor 1 - ind(.; h[0]) is present                          */
+  GPK_NODE_CP_HI = 32,      /* the factor ind(.; h[lo ? 1 : 0]) is present                     */
+  GPK_NODE_CP_SIGMOID = 64, /* mask form SIGMOID          (neither form bit: INDICATOR)        */
+  GPK_NODE_CP_APPROX = 128  /* mask form APPROX_INDICATOR                                      */
 };
 
 #define GPK_MAX_NODES 16
@@ -128,6 +144,9 @@ typedef struct {
 
 int gpk_abi_version(void);
 const char* gpk_last_error(void);
+/* 1 for every kernel-program op (GPK_OP_*) this library evaluates, else 0 (host only).  Ops are added without a new
+ * ABI number (programs that do not use them mean what they meant): a binding asks here before emitting a new one. */
+int gpk_op_supported(int32_t op);
 
 /* fill *out for the given shape (no device work) */
 int gpk_plan(int dtype, int32_t batch, int64_t n, int64_t m, int64_t d, gpk_layout* out);
@@ -422,6 +441,9 @@ int gpk_timing_reset(void);
  * "asm_f32_fast" (1: the f32 K build of a single SE / MAT32 / MAT52 node writes its interior tiles with f64
  * distances and the f32 hardware sqrt / exp -- a few f32 ulps from the f64 build; 0: every tile through the
  * general f64 evaluation, A/B; "asm_f32_chunk" (4) consecutive lower tiles per workgroup).
+ * "cp_skip" (1: on a tile where a change-point window leaf is exactly 0.0 for all 64 row points or all 64 column
+ * points, the K build does not evaluate the window's MUL sibling and pushes +0.0 -- equal under == to the unskipped
+ * value for finite sibling values; 0: every node on every tile, A/B).
  * "chain_xcd" (0; 1: the persistent launch's diagonal-chain tasks -- D, the next diagonal block's panel solves and
  * quarter updates -- as a second task list claimed first by up to "chain_xcd_seats" (16) workgroups of XCD 0, the
  * rest by everyone else, each workgroup falling back to the other list once its own is exhausted; measured no

@@ -1,8 +1,9 @@
-"""Base kernels SE / PER / MAT32 / MAT52 / LIN (gpbasics/KernelBasics/BaseKernels.py) on the device.
+"""Base kernels SE / PER / MAT32 / MAT52 / LIN / RQ (gpbasics/KernelBasics/BaseKernels.py) on the device.
 
 One table-driven class body serves the four stationary kernels on the hot path; each subclass only
 states its op code, its shape hyperparameters and its string name.  ``LinearKernel`` (the one
-non-stationary leaf) overrides the hyperparameter plumbing where it differs.  Semantics (formulae, DFS
+non-stationary leaf) overrides the hyperparameter plumbing where it differs, and so does
+``RationalQuadraticKernel`` for its dimensionless shape parameter ``a``.  Semantics (formulae, DFS
 hyperparameter order, default values, bounds, names, |l| normalisation in
 ``set_last_hyper_parameter``) follow the reference:
 
@@ -11,6 +12,8 @@ hyperparameter order, default values, bounds, names, |l| normalisation in
   MAT32  hyp [l, (sg)]      BaseKernels.py:697-851
   MAT52  hyp [l, (sg)]      BaseKernels.py:854-1011
   LIN    hyp [c, (sg)]      BaseKernels.py:110-270   c a vector of input_dimensionality offsets
+  RQ     hyp [l, a, (sg)]   (KernelManifestation.RQ = 103; the reference defines no formula: the standard
+                            (1 + s / (2 a l^2))^(-a) on the squared Euclidean distance s)
 
 ``sg`` exists only when ``global_parameters.p_scaled_base_kernel`` is True.
 
@@ -360,6 +363,76 @@ class LinearKernel(BaseKernel):
 
     def type_compare_to(self, other):
         return isinstance(other, LinearKernel)
+
+
+class RationalQuadraticKernel(BaseKernel):
+    """(1 + s / (2 a l^2))^(-a), s = sum_k (x_k - y_k)^2, times sg when scaled: the device's GPK_OP_RQ leaf, a scale
+    mixture of SE kernels (a -> inf is SE with the same l).  The reference names KernelManifestation.RQ and defines
+    no formula; this is the standard one.
+
+    Hyperparameters [l, a, (sg)], PER's slot layout.  ``l`` goes through the table like every length scale;
+    ``a`` is dimensionless, so it does not: default 1, random default |N(1, 0.2)|, bounds (1e-5, 1e5), and
+    ``get_last_hyper_parameter`` leaves it alone when it maps l back through the input scaling.  No ARD form
+    (``ard=True`` raises, as PeriodicKernel's), one distance form (no ``standard`` option)."""
+    _OP = nat.OP_RQ
+    _SHAPE = ("l", "a")
+    _ARD_CAPABLE = False
+    A_DEFAULT, A_STDDEV, A_BOUNDS = 1.0, 0.2, (1e-5, 1e5)
+
+    def __init__(self, input_dimensionality: int, ard: bool = False):
+        super().__init__(k.KernelManifestation.RQ, input_dimensionality, ard, None)
+
+    def uses_standard_form(self) -> bool:
+        return False
+
+    def _emit(self, nodes: list, offset: int, ard_slots: list, dim: int) -> int:
+        if not nat.op_supported(nat.OP_RQ):
+            raise nat.NativeUnavailable("this libgpk.so has no rational quadratic leaf (GPK_OP_RQ): rebuild it")
+        nodes.append((self._OP, offset, -1, nat.NODE_SCALED if global_param.p_scaled_base_kernel else 0))
+        return offset + self._n_values(dim)
+
+    def _shape_value(self, name, width):
+        if name == "a":
+            return torch.tensor(self.A_DEFAULT, dtype=torch.float64)
+        return super()._shape_value(name, width)
+
+    def get_default_hyper_parameter(self, xrange: List[List[float]], n: int, from_distribution: bool = False):
+        """Fixed: l = range width / 10, a = 1, sg = 0.1.  Random: l = |N(width / 10, 0.2)|, a = |N(1, 0.2)|,
+        sg = |N(0.1, 0.2)| (torch's generator)."""
+        if not from_distribution:
+            return super().get_default_hyper_parameter(xrange, n, False)
+        width = xrange[0][1] - xrange[0][0]
+        out = [torch.abs(torch.normal(width / 10.0, 0.2, size=[], dtype=torch.float64)),
+               torch.abs(torch.normal(self.A_DEFAULT, self.A_STDDEV, size=[], dtype=torch.float64))]
+        if global_param.p_scaled_base_kernel:
+            out.append(torch.abs(torch.normal(0.1, 0.2, size=[], dtype=torch.float64)))
+        return out
+
+    def get_hyper_parameter_distribution_definition(self, xrange: List[List[float]], n: int) -> List[dict]:
+        out = super().get_hyper_parameter_distribution_definition(xrange, n)
+        out[1] = {"shape": [], "mean": self.A_DEFAULT, "stddev": self.A_STDDEV, "type": "random_normal"}
+        return out
+
+    def get_hyper_parameter_bounds(self, xrange: List[List[float]], n: int) -> List[tuple]:
+        """l in [5 range / n, range / 3] (the table's); a in (1e-5, 1e5); sg in [100 jitter, inf)."""
+        out = super().get_hyper_parameter_bounds(xrange, n)
+        out[1] = (torch.tensor(self.A_BOUNDS[0], dtype=torch.float64), torch.tensor(self.A_BOUNDS[1], dtype=torch.float64))
+        return out
+
+    def get_last_hyper_parameter(self, scaling_x_param=None):
+        """l back in the unscaled inputs' units (times scale[1]); a and sg are dimensionless and stay."""
+        result = self.last_hyper_parameter
+        if scaling_x_param is None or result is None:
+            return result
+        return [result[0] * scaling_x_param[1]] + list(result[1:])
+
+    def deepcopy(self):
+        c = RationalQuadraticKernel(input_dimensionality=self.input_dimensionality)
+        if self.last_hyper_parameter is not None:
+            c.set_last_hyper_parameter(list(self.last_hyper_parameter))
+        if self.noise is not None:
+            c.set_noise(self.noise)
+        return c
 
 
 class ConstantKernel(BaseKernel):

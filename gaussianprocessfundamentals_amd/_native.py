@@ -17,6 +17,7 @@ from . import _build
 GPK_ABI_VERSION = 7
 GPK_F64, GPK_F32 = 0, 1
 OP_LIN, OP_PER, OP_SE, OP_MAT32, OP_MAT52, OP_ADD, OP_MUL = 102, 104, 105, 107, 108, 201, 202
+OP_RQ = 103   # rational quadratic leaf (1 + s / (2 a l^2))^(-a), hyp [l, a, (sg)]
 OP_CPW = 203  # change-point window leaf w(x) w(y) (the value of KernelManifestation.CP)
 NODE_SCALED, NODE_ARD, NODE_SE_EXPANDED, NODE_STANDARD = 1, 2, 4, 8
 NODE_CP_LO, NODE_CP_HI, NODE_CP_SIGMOID, NODE_CP_APPROX = 16, 32, 64, 128

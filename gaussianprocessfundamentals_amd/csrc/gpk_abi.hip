@@ -100,6 +100,14 @@ bool valid_kdesc(const gpk_kdesc* kd, int64_t d) {
       if (nd.hyp_offset < 0 || nd.hyp_offset + need > kd->n_hyp) return false;
       sp += 1;
       if (sp > 8) return false;
+    } else if (nd.op == GPK_OP_RQ) {
+      // [l, a, (sg)]: the direct squared distance of the raw points only -- no ARD slot, no other distance form
+      if (nd.flags & (GPK_NODE_ARD | GPK_NODE_SE_EXPANDED | GPK_NODE_STANDARD)) return false;
+      if (nd.ard_slot != -1) return false;
+      const int need = 2 + ((nd.flags & GPK_NODE_SCALED) ? 1 : 0);
+      if (nd.hyp_offset < 0 || nd.hyp_offset + need > kd->n_hyp) return false;
+      sp += 1;
+      if (sp > 8) return false;
     } else if (nd.op == GPK_OP_CPW) {
       // change-point window: 1-D inputs, one or two consecutive bounds, one mask form; reads the raw points
       if (kd->dim != 1) return false;
@@ -1022,7 +1030,7 @@ int gpk_abi_version(void) { return GPK_ABI_VERSION; }
 
 int gpk_op_supported(int32_t op) {
   switch (op) {
-    case GPK_OP_LIN: case GPK_OP_PER: case GPK_OP_SE: case GPK_OP_MAT32: case GPK_OP_MAT52:
+    case GPK_OP_LIN: case GPK_OP_RQ: case GPK_OP_PER: case GPK_OP_SE: case GPK_OP_MAT32: case GPK_OP_MAT52:
     case GPK_OP_ADD: case GPK_OP_MUL: case GPK_OP_CPW:
       return 1;
     default:
@@ -1502,7 +1510,7 @@ int gpk_nlml(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_dev, 
   if (!info_dev) return fail_arg(13, "info_dev");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   GPK_HIP(hipMemsetAsync(info_dev, 0, sizeof(int32_t) * lay->batch, s), "memset info");
-  // Fused K build (single SE / MAT32 / MAT52 nodes; any other single node, LIN included, takes the plain assemble
+  // Fused K build (single SE / MAT32 / MAT52 nodes; any other single node, LIN and RQ included, takes the plain assemble
   // launch and the unfused factorisation below): only the first panel group's block columns are
   // assembled; the first trailing update evaluates its C tiles instead of reading them, so the
   // trailing part of K is never written to HBM and read back.
@@ -1649,6 +1657,7 @@ int gpk_potrf_lower(int dtype, void* A, int64_t n, int64_t lda, void* work, size
 
 size_t gpk_grad_workspace_bytes(const gpk_kdesc* kd, const gpk_layout* lay) {
   if (!kd || !lay || lay->n <= 0 || lay->batch <= 0) return 0;
+  if (!valid_kdesc(kd, lay->d)) return 0;  // (gpk_nlml_grad refuses such a program: no workspace to size)
   const int64_t nt = (lay->n + ATILE - 1) / ATILE;
   return (size_t)lay->batch * (size_t)(nt * (nt + 1) / 2) * (size_t)(kd->n_hyp + 1) * sizeof(double);
 }

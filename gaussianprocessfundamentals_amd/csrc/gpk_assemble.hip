@@ -18,6 +18,7 @@
 //   MAT32  KernelBasics/BaseKernels.py:702-720   (1 + f) e^-f,            f = (sqrt3 d1) / |l|
 //   MAT52  KernelBasics/BaseKernels.py:859-880   ((1 + f) + 5 d1^2 / (3 l^2)) e^-f,  f = (sqrt5 d1) / |l|
 //   LIN    KernelBasics/BaseKernels.py:114-134   (x - c)(y - c)^T over the dimensions, c one offset per dimension
+//   RQ     (no reference formula; KernelManifestation.RQ = 103)   (1 + s / (2 a l^2))^(-a), s = squared Euclidean
 //   ADD/MUL KernelBasics/Operators.py:207-225, :306-326 (left fold over children)
 //   CPW    KernelBasics/Operators.py:379-476      the change-point operator's mask of one child, w(x) w(y) with
 //          w(x) = (1 - ind(x; cp_prev)) ind(x; cp): a leaf that multiplies its child (gpk_kernels.h, cp_window);
@@ -165,16 +166,18 @@ __device__ __forceinline__ void interior_single(FastNode fn, const double* prow,
   for (int rr = r0; rr < ATILE; rr += 4) {
     const double* pa = prow + fn.off + rr * dp;
     double v = GPK_ASM_ABLATE ? 0.0
-                              : fast_value_at_c(fn, [pa](int k) { return pa[k]; }, [&cb](int k) { return cb[k]; },
-                                                [&cc](int k) { return cc[k]; });
+                              : fast_value_at_c<OP == GPK_OP_RQ>(fn, [pa](int k) { return pa[k]; },
+                                                                 [&cb](int k) { return cb[k]; },
+                                                                 [&cc](int k) { return cc[k]; });
     const int64_t gi = gi0 + rr;
     if (gi == gj) v += noise;
     W[gi * ld + gj] = (TOut)v;
   }
 }
 
-// trees whose base nodes read the raw points or ONE ARD slot (slot offset off1)
-template <typename TOut, int D>
+// trees whose base nodes read the raw points or ONE ARD slot (slot offset off1); RQL: the instantiation for
+// programs with rational quadratic leaves (the only one that carries their code, rq_leaves)
+template <typename TOut, int D, bool RQL>
 __device__ __forceinline__ void interior_tree(const gpk_kdesc& kd, const FastNode* fns, const double* prow,
                                               const double* pcol, int off1, int dp, int c, int r0, int64_t gi0,
                                               int64_t gj, double noise, TOut* W, int64_t ld, int sc_sin, int sc_cos,
@@ -221,8 +224,8 @@ __device__ __forceinline__ void interior_tree(const gpk_kdesc& kd, const FastNod
         } else {
           const bool s1 = f.off != 0;
           const double* pa = prow + f.off + rr * dp;
-          st.set(sp, fast_value_at(f, [pa](int k) { return pa[k]; },
-                                   [&cb0, &cb1, s1](int k) { return s1 ? cb1[k] : cb0[k]; }));
+          st.set(sp, fast_value_at<RQL>(f, [pa](int k) { return pa[k]; },
+                                        [&cb0, &cb1, s1](int k) { return s1 ? cb1[k] : cb0[k]; }));
         }
         sp += 1;
       }
@@ -292,8 +295,9 @@ __device__ __forceinline__ void leaf_dispatch(const FastNode& f, bool sc_on, con
     case GPK_OP_MAT32: leaf_rows<D, GPK_OP_MAT32>(f, prow, pcol, dp, c, r0, mode, acc); break;
     case GPK_OP_MAT52: leaf_rows<D, GPK_OP_MAT52>(f, prow, pcol, dp, c, r0, mode, acc); break;
     case GPK_OP_LIN: leaf_rows<D, GPK_OP_LIN>(f, prow, pcol, dp, c, r0, mode, acc); break;
-    default:  // (no such leaf passes valid_kdesc -- a program with a window leaf, GPK_OP_CPW, never takes this two-leaf
-              // path, launch_assemble; were one to, NaN rather than another op's formula)
+    default:  // (no such leaf passes valid_kdesc -- a program with a window leaf, GPK_OP_CPW, or a rational quadratic
+              // leaf, GPK_OP_RQ, never takes this two-leaf path, launch_assemble: both have the instantiation that
+              // carries their code; were one to, NaN rather than another op's formula)
 #pragma unroll
       for (int i = 0; i < ATILE / 4; ++i) acc[i] = NAN;
       break;
@@ -554,8 +558,9 @@ __device__ __forceinline__ void pair_mfma_tile(const gpk_kdesc& kd, const AsmArg
   }
 }
 
-// TREE: 0 single base node, 1 general tree, 2 two-leaf tree (interior_pair)
-template <typename TOut, int D, int TREE>
+// TREE: 0 single base node, 1 general tree, 2 two-leaf tree (interior_pair); RQL: the general tree instantiation for
+// programs with rational quadratic leaves (a single RQ node keeps the single-node interior loop inside it)
+template <typename TOut, int D, int TREE, bool RQL>
 __device__ __forceinline__ bool interior_d(const gpk_kdesc& kd, const FastNode& fn, const FastNode* fns, bool fast,
                                            const double* prow, const double* pcol, int slot_stride, int dp, int c,
                                            int r0, int64_t gi0, int64_t gj, double noise, TOut* W, int64_t ld,
@@ -571,6 +576,12 @@ __device__ __forceinline__ bool interior_d(const gpk_kdesc& kd, const FastNode& 
       case GPK_OP_MAT32: interior_single<TOut, D, GPK_OP_MAT32>(fn, prow, pcol, dp, c, r0, gi0, gj, noise, W, ld); return true;
       case GPK_OP_MAT52: interior_single<TOut, D, GPK_OP_MAT52>(fn, prow, pcol, dp, c, r0, gi0, gj, noise, W, ld); return true;
       case GPK_OP_LIN: interior_single<TOut, D, GPK_OP_LIN>(fn, prow, pcol, dp, c, r0, gi0, gj, noise, W, ld); return true;
+      case GPK_OP_RQ:
+        if constexpr (RQL) {
+          interior_single<TOut, D, GPK_OP_RQ>(fn, prow, pcol, dp, c, r0, gi0, gj, noise, W, ld);
+          return true;
+        }
+        return false;
       default: return false;  // (an op without an interior loop: the generic loop below evaluates it)
     }
   }
@@ -581,8 +592,8 @@ __device__ __forceinline__ bool interior_d(const gpk_kdesc& kd, const FastNode& 
   // (programs of more than 8 nodes keep the generic loop -- except change-point trees, 7 / 11 / 15 nodes for two to
   // four single-leaf children, most of whose nodes the interior loop skips on most tiles)
   if (!TREE || GPK_ASM_INTERIOR_TREE == 0 || kd.n_ard > 1 || (kd.n_nodes > 8 && nw == 0)) return false;
-  interior_tree<TOut, D>(kd, fns, prow, pcol, slot_stride, dp, c, r0, gi0, gj, noise, W, ld, sc_sin, sc_cos, sc_on,
-                         cp_zero);
+  interior_tree<TOut, D, RQL>(kd, fns, prow, pcol, slot_stride, dp, c, r0, gi0, gj, noise, W, ld, sc_sin, sc_cos, sc_on,
+                              cp_zero);
   return true;
 }
 
@@ -995,7 +1006,7 @@ __global__ __launch_bounds__(256) void f32_fast_kernel(gpk_kdesc kd, AsmArgs a, 
 #ifndef GPK_ASM3_MINB
 #define GPK_ASM3_MINB 3  // TREE 3: workgroups per CU the register allocation must allow (A/B)
 #endif
-template <typename TOut, int TREE>
+template <typename TOut, int TREE, bool RQL>
 __device__ __forceinline__ void assemble_tile(const gpk_kdesc& kd, const AsmArgs& a, int64_t ti, int64_t tj, int b,
                                               double* smem, int& sc_flag, unsigned long long* pair_max) {
   const int slot_stride = ATILE * a.dp;
@@ -1026,7 +1037,7 @@ __device__ __forceinline__ void assemble_tile(const gpk_kdesc& kd, const AsmArgs
   if ((kd.n_nodes > 1 || nw > 0) && tid < kd.n_nodes) {
     const gpk_node nd = kd.nodes[tid];
     if (nd.op != GPK_OP_ADD && nd.op != GPK_OP_MUL) {
-      FastNode f = make_fast_node(nd, hyp_s, a.d);
+      FastNode f = make_fast_node<RQL>(nd, hyp_s, a.d);
       f.off = (nd.flags & GPK_NODE_ARD) ? (nd.ard_slot + 1) * slot_stride : 0;
       if (nd.op == GPK_OP_CPW && nw > 0) {
         int kw = 0;  // its rank among the window leaves: the slot stage_points fills for it
@@ -1109,14 +1120,14 @@ __device__ __forceinline__ void assemble_tile(const gpk_kdesc& kd, const AsmArgs
       if (a.uplo && gj > gi) continue;
       double v;
       if (kd.n_nodes == 1 && nw == 0) {
-        FastNode f1 = make_fast_node(kd.nodes[0], hyp_s, a.d);
+        FastNode f1 = make_fast_node<RQL>(kd.nodes[0], hyp_s, a.d);
         f1.sc = scq == 0 ? 1 : 0;
         f1.sc_sin = sc_sin;
         f1.sc_cos = sc_cos;
-        v = fast_value(f1, prow + rr * a.dp + fast_off(kd, slot_stride), pcol + c * a.dp + fast_off(kd, slot_stride),
-                       sc_on);
+        v = fast_value<RQL>(f1, prow + rr * a.dp + fast_off(kd, slot_stride),
+                            pcol + c * a.dp + fast_off(kd, slot_stride), sc_on);
       } else {
-        v = eval_tree_fast<WIN>(kd, fns, prow + rr * a.dp, pcol + c * a.dp, sc_on, cp_zero);
+        v = eval_tree_fast<WIN, RQL>(kd, fns, prow + rr * a.dp, pcol + c * a.dp, sc_on, cp_zero);
       }
       if (gi == gj) v += a.diag_add;
       W[gi * a.ld + gj] = (TOut)v;
@@ -1129,7 +1140,7 @@ __device__ __forceinline__ void assemble_tile(const gpk_kdesc& kd, const AsmArgs
   const double yv = (ccls == CLS_TRAIN) ? a.y[(int64_t)b * a.y_bs + gj] : 0.0;
   const bool col_kernel = (ccls == CLS_TRAIN || ccls == CLS_TEST);
   const bool fast = kd.n_nodes == 1 && nw == 0;
-  FastNode fn = make_fast_node(kd.nodes[0], hyp_s, a.d);
+  FastNode fn = make_fast_node<RQL>(kd.nodes[0], hyp_s, a.d);
   fn.off = fast_off(kd, slot_stride);
   fn.sc = scq == 0 ? 1 : 0;
   fn.sc_sin = sc_sin;
@@ -1137,11 +1148,11 @@ __device__ __forceinline__ void assemble_tile(const gpk_kdesc& kd, const AsmArgs
   if (TREE != 3 && GPK_ASM_INTERIOR && !a.generic && a.A == nullptr && gi0 + ATILE <= nm) {  // lower tiles: gj0 <= gi0
     bool done = false;
     switch (a.d) {
-      case 1: done = interior_d<TOut, 1, TREE>(kd, fn, fns, fast, prow, pcol, slot_stride, a.dp, c, r0, gi0, gj, noise, W, a.ld, sc_sin, sc_cos, sc_on, nw, cp_zero); break;
-      case 2: done = interior_d<TOut, 2, TREE>(kd, fn, fns, fast, prow, pcol, slot_stride, a.dp, c, r0, gi0, gj, noise, W, a.ld, sc_sin, sc_cos, sc_on, nw, cp_zero); break;
-      case 3: done = interior_d<TOut, 3, TREE>(kd, fn, fns, fast, prow, pcol, slot_stride, a.dp, c, r0, gi0, gj, noise, W, a.ld, sc_sin, sc_cos, sc_on, nw, cp_zero); break;
-      case 4: done = interior_d<TOut, 4, TREE>(kd, fn, fns, fast, prow, pcol, slot_stride, a.dp, c, r0, gi0, gj, noise, W, a.ld, sc_sin, sc_cos, sc_on, nw, cp_zero); break;
-      case 8: done = interior_d<TOut, 8, TREE>(kd, fn, fns, fast, prow, pcol, slot_stride, a.dp, c, r0, gi0, gj, noise, W, a.ld, sc_sin, sc_cos, sc_on, nw, cp_zero); break;
+      case 1: done = interior_d<TOut, 1, TREE, RQL>(kd, fn, fns, fast, prow, pcol, slot_stride, a.dp, c, r0, gi0, gj, noise, W, a.ld, sc_sin, sc_cos, sc_on, nw, cp_zero); break;
+      case 2: done = interior_d<TOut, 2, TREE, RQL>(kd, fn, fns, fast, prow, pcol, slot_stride, a.dp, c, r0, gi0, gj, noise, W, a.ld, sc_sin, sc_cos, sc_on, nw, cp_zero); break;
+      case 3: done = interior_d<TOut, 3, TREE, RQL>(kd, fn, fns, fast, prow, pcol, slot_stride, a.dp, c, r0, gi0, gj, noise, W, a.ld, sc_sin, sc_cos, sc_on, nw, cp_zero); break;
+      case 4: done = interior_d<TOut, 4, TREE, RQL>(kd, fn, fns, fast, prow, pcol, slot_stride, a.dp, c, r0, gi0, gj, noise, W, a.ld, sc_sin, sc_cos, sc_on, nw, cp_zero); break;
+      case 8: done = interior_d<TOut, 8, TREE, RQL>(kd, fn, fns, fast, prow, pcol, slot_stride, a.dp, c, r0, gi0, gj, noise, W, a.ld, sc_sin, sc_cos, sc_on, nw, cp_zero); break;
       default: break;
     }
     if (done) return;
@@ -1167,8 +1178,8 @@ __device__ __forceinline__ void assemble_tile(const gpk_kdesc& kd, const AsmArgs
       if (gi == gj) v += noise;
     } else if ((rcls == CLS_TRAIN || rcls == CLS_TEST) && col_kernel) {
       if (!GPK_ASM_ABLATE)
-        v = fast ? fast_value(fn, prow + fn.off + rr * a.dp, pcol + fn.off + c * a.dp, sc_on)
-                 : eval_tree_fast<WIN>(kd, fns, prow + rr * a.dp, pcol + c * a.dp, sc_on, cp_zero);
+        v = fast ? fast_value<RQL>(fn, prow + fn.off + rr * a.dp, pcol + fn.off + c * a.dp, sc_on)
+                 : eval_tree_fast<WIN, RQL>(kd, fns, prow + rr * a.dp, pcol + c * a.dp, sc_on, cp_zero);
       if (rcls == CLS_TRAIN && ccls == CLS_TRAIN && gi == gj) v += noise;
     } else if (rcls == CLS_Y && ccls == CLS_TRAIN) {
       v = yv;
@@ -1186,8 +1197,11 @@ __global__ __launch_bounds__(256, TREE == 3 ? GPK_ASM3_MINB : 1) void assemble_k
   // bounds -- in a persistent loop; an instantiation of its own without the register bound of TREE 3's, whose
   // occupancy its few tiles do not need)
   // (TREE 5: TREE 0's body over the tile list f32_fast_kernel left)
-  constexpr int TB = TREE == 4 ? 3 : TREE == 5 ? 0 : TREE;
-  const bool list = TREE >= 4;
+  // (TREE 6: TREE 1's body with the rational quadratic leaf's code, for every program with such a leaf -- single
+  // node, pair or tree, with or without windows: log1p on top of exp takes registers that would cost the other
+  // instantiations their occupancy)
+  constexpr int TB = TREE == 4 ? 3 : TREE == 5 ? 0 : TREE == 6 ? 1 : TREE;
+  const bool list = TREE == 4 || TREE == 5;  // (6 walks the grid like 1: it has no tile list, a.tlist is null there)
   const int cnt = list ? a.tlist[0] : 1;
   for (int e = list ? (int)blockIdx.x : 0; e < cnt; e += list ? (int)gridDim.x : 1) {
     int b;
@@ -1207,7 +1221,7 @@ __global__ __launch_bounds__(256, TREE == 3 ? GPK_ASM3_MINB : 1) void assemble_k
       b = blockIdx.y;
       lower_tile(a, blockIdx.x, ti, tj);
     }
-    assemble_tile<TOut, TB>(kd, a, ti, tj, b, smem, sc_flag, pair_max);
+    assemble_tile<TOut, TB, TREE == 6>(kd, a, ti, tj, b, smem, sc_flag, pair_max);
   }
 }
 
@@ -1224,6 +1238,7 @@ __global__ __launch_bounds__(256, TREE == 3 ? GPK_ASM3_MINB : 1) void assemble_k
 
 // values of every node of the postfix program (node q's value = its subtree's value) into the
 // thread's LDS column v[q * 256]
+template <bool RQL>
 __device__ __forceinline__ void eval_nodes(const gpk_kdesc& kd, const double* hyp, const double* pa,
                                            const double* pb, int slot_stride, int d, double* v) {
   Stack st;
@@ -1239,7 +1254,7 @@ __device__ __forceinline__ void eval_nodes(const gpk_kdesc& kd, const double* hy
       sp -= 1;
     } else {
       const int off = (nd.flags & GPK_NODE_ARD) ? (nd.ard_slot + 1) * slot_stride : 0;
-      st.set(sp, base_value(nd, hyp, pa + off, pb + off, d));
+      st.set(sp, base_value<RQL>(nd, hyp, pa + off, pb + off, d));
       sp += 1;
     }
     v[q * 256] = st.get(sp - 1);
@@ -1249,7 +1264,9 @@ __device__ __forceinline__ void eval_nodes(const gpk_kdesc& kd, const double* hy
 constexpr int GNP = GPK_MAX_DIM + 1;  // hyperparameters of one base node, at most (ARD l + sg)
 
 // acc[k] += coef * d k_node / d h[k] for the node's hyperparameters h (reference formulas, see the
-// citations at the top of this file; |l| of the Matern kernels differentiates to sign(l)).
+// citations at the top of this file; |l| of the Matern kernels differentiates to sign(l)).  RQL: the instantiation
+// for programs with rational quadratic leaves (rq_leaves): the others carry none of that leaf's code.
+template <bool RQL>
 __device__ __forceinline__ void base_partials(const gpk_node& nd, const double* __restrict__ hyp,
                                               const double* a, const double* b, int d, double coef,
                                               double (&acc)[GNP]) {
@@ -1306,6 +1323,24 @@ __device__ __forceinline__ void base_partials(const gpk_node& nd, const double* 
         acc[k] -= coef * sg * (ta + tb);
       }
     if (scaled) acc[GPK_MAX_DIM] += coef * s;
+    return;
+  }
+  if (RQL && nd.op == GPK_OP_RQ) {
+    // k = sg q^(-a), q = 1 + u, u = s / (2 a l^2): d k / d l = k s / (l^3 q), d k / d a = k g(u) with
+    // g = u / q - log1p(u) (rq_g: a series where the two terms cancel), d k / d sg the unscaled value
+    double s = 0.0;
+    for (int k = 0; k < d; ++k) {
+      const double t = a[k] - b[k];
+      s += t * t;
+    }
+    const double l = h[0], av = h[1];
+    const double sg = scaled ? h[2] : 1.0;
+    const double iu = rq_iu(l, av);
+    const double u = s * iu;
+    const double r = rq_value(s, iu, av);
+    acc[0] += coef * sg * r * s / ((l * l * l) * (1.0 + u));
+    acc[1] += coef * sg * r * rq_g(u);
+    if (scaled) acc[2] += coef * r;
     return;
   }
   if (nd.op == GPK_OP_CPW) {
@@ -1397,7 +1432,7 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;
 }
 
-template <typename T>
+template <typename T, bool RQL>
 __global__ __launch_bounds__(256) void grad_kernel(gpk_kdesc kd, AsmArgs a, GradArgs g) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int slot_stride = ATILE * a.dp;
@@ -1463,18 +1498,18 @@ __global__ __launch_bounds__(256) void grad_kernel(gpk_kdesc kd, AsmArgs a, Grad
       if (qk == 0.0) continue;
       double adj = 1.0;
       if (mask != 0u) {
-        eval_nodes(kd, hyp_s, prow + rr * a.dp, pcol + c * a.dp, slot_stride, a.d, vals + tid);
+        eval_nodes<RQL>(kd, hyp_s, prow + rr * a.dp, pcol + c * a.dp, slot_stride, a.d, vals + tid);
 #pragma unroll 1
         for (int q = 0; q < kd.n_nodes; ++q)
           if (mask & (1u << q)) adj *= vals[q * 256 + tid];
       }
-      base_partials(nd, hyp_s, prow + off + rr * a.dp, pcol + off + c * a.dp, a.d, qk * adj, acc);
+      base_partials<RQL>(nd, hyp_s, prow + off + rr * a.dp, pcol + off + c * a.dp, a.d, qk * adj, acc);
     }
     // hyperparameter slots of this node: ARD l_0..l_{d-1} then sg (stored at acc[GPK_MAX_DIM])
     const bool ard = (nd.flags & GPK_NODE_ARD) != 0;
     const bool vec = ard || nd.op == GPK_OP_LIN;  // d vector entries (ARD l, LIN c), then sg
     const bool win = nd.op == GPK_OP_CPW;         // its one or two bounds, no sg
-    const int nshape = win ? cp_bounds(nd.flags) : vec ? a.d : (nd.op == GPK_OP_PER ? 2 : 1);
+    const int nshape = win ? cp_bounds(nd.flags) : vec ? a.d : ((nd.op == GPK_OP_PER || nd.op == GPK_OP_RQ) ? 2 : 1);
     const bool scaled = (nd.flags & GPK_NODE_SCALED) != 0;
     const bool sg_moved = vec && scaled;
     const int np = nshape + (scaled ? 1 : 0);
@@ -1535,6 +1570,7 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(GradArgs g, int64_t nt
 // give TensorFlow's 0 * inf = NaN there -- the analytic limit 0 is returned instead).
 
 // acc_z[k] += coef * d k_node(a, b) / d b_k in the node's own coordinates (ARD nodes: scaled points)
+template <bool RQL>
 __device__ __forceinline__ void base_input_partials(const gpk_node& nd, const double* __restrict__ hyp,
                                                     const double* a, const double* b, int d, double coef,
                                                     double (&acc)[GPK_MAX_DIM]) {
@@ -1555,10 +1591,23 @@ __device__ __forceinline__ void base_input_partials(const gpk_node& nd, const do
     acc[0] -= coef * cp_window(fl, h, a[0]) * (db[0] + db[1]);
     return;
   }
-  const double v = base_value(nd, hyp, a, b, d);  // includes sg
+  const double v = base_value<RQL>(nd, hyp, a, b, d);  // includes sg
   if (nd.op == GPK_OP_SE) {
     const double l = ard ? 1.0 : h[0];
     const double c = coef * v / (l * l);
+#pragma unroll
+    for (int k = 0; k < GPK_MAX_DIM; ++k)
+      if (k < d) acc[k] += c * (a[k] - b[k]);
+    return;
+  }
+  if (RQL && nd.op == GPK_OP_RQ) {  // d k / d b_k = k (a_k - b_k) / (l^2 q), q = 1 + s / (2 a l^2): 0 at coincident points
+    const double l = h[0];
+    double s = 0.0;
+    for (int k = 0; k < d; ++k) {
+      const double t = a[k] - b[k];
+      s += t * t;
+    }
+    const double c = coef * v / ((l * l) * (1.0 + s * rq_iu(l, h[1])));
 #pragma unroll
     for (int k = 0; k < GPK_MAX_DIM; ++k)
       if (k < d) acc[k] += c * (a[k] - b[k]);
@@ -1623,6 +1672,7 @@ __device__ __forceinline__ void base_input_partials(const gpk_node& nd, const do
 // one 64 x 64 tile of K(X, Z) per workgroup (row tile ti = blockIdx.y, column tile tj = blockIdx.x);
 // lane = column, wave w = rows w, w + 4, ...; per-tile partial sums to the workspace, reduced in a
 // fixed order by vjp_reduce_kernel (deterministic)
+template <bool RQL>
 __global__ __launch_bounds__(256) void vjp_kernel(gpk_kdesc kd, AsmArgs a, VjpArgs g) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int slot_stride = ATILE * a.dp;
@@ -1668,13 +1718,13 @@ __global__ __launch_bounds__(256) void vjp_kernel(gpk_kdesc kd, AsmArgs a, VjpAr
       if (qk == 0.0) continue;
       double adj = 1.0;
       if (mask != 0u) {
-        eval_nodes(kd, hyp_s, prow + rr * a.dp, pcol + c * a.dp, slot_stride, a.d, vals + tid);
+        eval_nodes<RQL>(kd, hyp_s, prow + rr * a.dp, pcol + c * a.dp, slot_stride, a.d, vals + tid);
 #pragma unroll 1
         for (int q = 0; q < kd.n_nodes; ++q)
           if (mask & (1u << q)) adj *= vals[q * 256 + tid];
       }
-      base_partials(nd, hyp_s, prow + off + rr * a.dp, pcol + off + c * a.dp, a.d, qk * adj, acc);
-      if (g.want_z) base_input_partials(nd, hyp_s, prow + off + rr * a.dp, pcol + off + c * a.dp, a.d, qk * adj, az);
+      base_partials<RQL>(nd, hyp_s, prow + off + rr * a.dp, pcol + off + c * a.dp, a.d, qk * adj, acc);
+      if (g.want_z) base_input_partials<RQL>(nd, hyp_s, prow + off + rr * a.dp, pcol + off + c * a.dp, a.d, qk * adj, az);
     }
     // raw coordinates: an ARD node sees z_k / l_k
 #pragma unroll
@@ -1682,7 +1732,7 @@ __global__ __launch_bounds__(256) void vjp_kernel(gpk_kdesc kd, AsmArgs a, VjpAr
       if (k < a.d) gz[k] += ard ? az[k] / hyp_s[nd.hyp_offset + k] : az[k];
     const bool vec = ard || nd.op == GPK_OP_LIN;  // d vector entries (ARD l, LIN c), then sg
     const bool win = nd.op == GPK_OP_CPW;         // its one or two bounds, no sg
-    const int nshape = win ? cp_bounds(nd.flags) : vec ? a.d : (nd.op == GPK_OP_PER ? 2 : 1);
+    const int nshape = win ? cp_bounds(nd.flags) : vec ? a.d : ((nd.op == GPK_OP_PER || nd.op == GPK_OP_RQ) ? 2 : 1);
     const bool scaled = (nd.flags & GPK_NODE_SCALED) != 0;
     const bool sg_moved = vec && scaled;
     const int np = nshape + (scaled ? 1 : 0);
@@ -1762,12 +1812,14 @@ hipError_t launch_vjp(const gpk_kdesc& kd, const VjpArgs& g0, const double* X, i
   const size_t lds = sizeof(double) * (GPK_MAX_HYP + 4 * GNP + 4 * (size_t)ATILE * d +
                                        2 * (size_t)(1 + kd.n_ard) * ATILE * a.dp +
                                        (has_mul ? (size_t)kd.n_nodes * 256 : 0));
+  // (a program with a rational quadratic leaf: the instantiation that carries the leaf's code, rq_leaves)
+  const auto vjp = rq_leaves(kd) > 0 ? vjp_kernel<true> : vjp_kernel<false>;
   {
-    hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(vjp_kernel), lds);  // (d = 16, two ARD nodes: 118 KB)
+    hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(vjp), lds);  // (d = 16, two ARD nodes: 118 KB)
     if (e != hipSuccess) return e;
   }
   if (kd.n_hyp > 0) {
-    hipLaunchKernelGGL(vjp_kernel, dim3((unsigned)tc, (unsigned)tr), dim3(256), lds, s, kd, a, g);
+    hipLaunchKernelGGL(vjp, dim3((unsigned)tc, (unsigned)tr), dim3(256), lds, s, kd, a, g);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(vjp_reduce_kernel, dim3((unsigned)kd.n_hyp), dim3(256), 0, s, g.part_h, tr * tc,
@@ -1775,7 +1827,7 @@ hipError_t launch_vjp(const gpk_kdesc& kd, const VjpArgs& g0, const double* X, i
     e = hipGetLastError();
     if (e != hipSuccess) return e;
   } else if (g.want_z) {
-    hipLaunchKernelGGL(vjp_kernel, dim3((unsigned)tc, (unsigned)tr), dim3(256), lds, s, kd, a, g);
+    hipLaunchKernelGGL(vjp, dim3((unsigned)tc, (unsigned)tr), dim3(256), lds, s, kd, a, g);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
@@ -1809,15 +1861,15 @@ hipError_t launch_grad(const gpk_kdesc& kd, const GradArgs& g, int dtype, int32_
                                        2 * (size_t)(1 + kd.n_ard) * ATILE * a.dp +
                                        (has_mul ? (size_t)kd.n_nodes * 256 : 0));
   dim3 grid((unsigned)ntri, (unsigned)batch, 1);
+  // (a program with a rational quadratic leaf: the instantiation that carries the leaf's code, rq_leaves)
+  const bool rq = rq_leaves(kd) > 0;
+  const auto grad = dtype == GPK_F64 ? (rq ? grad_kernel<double, true> : grad_kernel<double, false>)
+                                     : (rq ? grad_kernel<float, true> : grad_kernel<float, false>);
   {
-    hipError_t e = ensure_dyn_lds(dtype == GPK_F64 ? reinterpret_cast<const void*>(grad_kernel<double>)
-                                                   : reinterpret_cast<const void*>(grad_kernel<float>), lds);
+    hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(grad), lds);
     if (e != hipSuccess) return e;
   }
-  if (dtype == GPK_F64)
-    hipLaunchKernelGGL(grad_kernel<double>, grid, dim3(256), lds, s, kd, a, g);
-  else
-    hipLaunchKernelGGL(grad_kernel<float>, grid, dim3(256), lds, s, kd, a, g);
+  hipLaunchKernelGGL(grad, grid, dim3(256), lds, s, kd, a, g);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)(kd.n_hyp + 1), (unsigned)batch), dim3(256), 0, s,
@@ -1886,6 +1938,10 @@ hipError_t launch_assemble(const gpk_kdesc& kd, const AsmArgs& a_in, int dtype, 
   // (a window leaf is evaluated by the general tree instantiation only: a program with one takes tree 1 whatever its
   // size -- a change-point tree has at least 7 nodes anyway)
   int tree = (kd.n_nodes == 1 && nw == 0) ? 0 : (pair && nw == 0 && !tune_pair_off() ? 2 : 1);
+  // (a rational quadratic leaf likewise: instantiation 6, the general tree body with the leaf's code, for a single RQ
+  // node -- which keeps the single-node interior loop there -- as for any tree with one; the MFMA pair path and the f32
+  // kernel below need tree 2 / tree 0 and so never see such a program)
+  if (rq_leaves(kd) > 0) tree = 6;
   if (tree == 2 && GPK_ASM_PAIR_MFMA && a.A == nullptr && a.d % 4 == 0 && dtype == GPK_F64) {
     const int q = sc_node(kd);
     const gpk_node se = kd.nodes[q == 0 ? 1 : 0];
@@ -1952,7 +2008,8 @@ hipError_t launch_assemble(const gpk_kdesc& kd, const AsmArgs& a_in, int dtype, 
     const gpk_node nd = kd.nodes[0];
     const bool se = nd.op == GPK_OP_SE && !(nd.flags & GPK_NODE_SE_EXPANDED);
     const bool mat = nd.op == GPK_OP_MAT32 || nd.op == GPK_OP_MAT52;
-    // (any other single node -- PER, the expanded SE, LIN -- has no f32 kernel: the general instantiation below)
+    // (any other single node -- PER, the expanded SE, LIN -- has no f32 kernel: the general instantiation below; a
+    // single RQ node never comes here: tree 6)
     // every tile interior (training rows and columns) or tail (y / zero rows): n = n_pad, no test, identity or
     // dense rows, no ragged members -- then no edge tile can occur and the kernel runs alone (no list, no memset)
     const bool no_edges = a.n == a.n_pad && a.m == 0 && !a.nb && !a.mb && !a.eye && a.E == nullptr &&
@@ -2006,12 +2063,14 @@ hipError_t launch_assemble(const gpk_kdesc& kd, const AsmArgs& a_in, int dtype, 
   // slots, at d = 16: 71 KB; two ARD nodes: 87 KB -- the kernel's dynamic-LDS limit must be raised first)
   {
     const void* fn = dtype == GPK_F64
-                         ? (af.tlist != nullptr ? reinterpret_cast<const void*>(assemble_kernel<double, 4>)
+                         ? (tree == 6 ? reinterpret_cast<const void*>(assemble_kernel<double, 6>)
+                            : af.tlist != nullptr ? reinterpret_cast<const void*>(assemble_kernel<double, 4>)
                             : tree == 3 ? reinterpret_cast<const void*>(assemble_kernel<double, 3>)
                             : tree == 2 ? reinterpret_cast<const void*>(assemble_kernel<double, 2>)
                                       : tree == 1 ? reinterpret_cast<const void*>(assemble_kernel<double, 1>)
                                                   : reinterpret_cast<const void*>(assemble_kernel<double, 0>))
-                         : (tree == 5 ? reinterpret_cast<const void*>(assemble_kernel<float, 5>)
+                         : (tree == 6 ? reinterpret_cast<const void*>(assemble_kernel<float, 6>)
+                            : tree == 5 ? reinterpret_cast<const void*>(assemble_kernel<float, 5>)
                             : tree == 2 ? reinterpret_cast<const void*>(assemble_kernel<float, 2>)
                                       : tree == 1 ? reinterpret_cast<const void*>(assemble_kernel<float, 1>)
                                                   : reinterpret_cast<const void*>(assemble_kernel<float, 0>));
@@ -2020,7 +2079,9 @@ hipError_t launch_assemble(const gpk_kdesc& kd, const AsmArgs& a_in, int dtype, 
   }
   if (af.tlist != nullptr && dtype == GPK_F64) tree = 4;
   if (dtype == GPK_F64) {
-    if (tree == 4)
+    if (tree == 6)
+      hipLaunchKernelGGL((assemble_kernel<double, 6>), grid, dim3(256), lds, s, kd, a);
+    else if (tree == 4)
       hipLaunchKernelGGL((assemble_kernel<double, 4>), grid, dim3(256), lds, s, kd, af);
     else if (tree == 3)
       hipLaunchKernelGGL((assemble_kernel<double, 3>), grid, dim3(256), lds, s, kd, af);
@@ -2031,7 +2092,9 @@ hipError_t launch_assemble(const gpk_kdesc& kd, const AsmArgs& a_in, int dtype, 
     else
       hipLaunchKernelGGL((assemble_kernel<double, 0>), grid, dim3(256), lds, s, kd, a);
   } else {
-    if (tree == 5)
+    if (tree == 6)
+      hipLaunchKernelGGL((assemble_kernel<float, 6>), grid, dim3(256), lds, s, kd, a);
+    else if (tree == 5)
       hipLaunchKernelGGL((assemble_kernel<float, 5>), grid, dim3(256), lds, s, kd, af);
     else if (tree == 2)
       hipLaunchKernelGGL((assemble_kernel<float, 2>), grid, dim3(256), lds, s, kd, a);

@@ -111,9 +111,61 @@ __host__ __device__ inline int cp_skip_to(const gpk_kdesc& kd, int q) {
   return 0;
 }
 
+// ------------------------------------------------------------------ rational quadratic leaf (GPK_OP_RQ)
+// k = (1 + u)^(-a) = exp(-a log1p(u)), u = s / (2 a l^2), s the squared Euclidean distance (SE's direct sum).  ONE
+// pair of functions with one operation order computes it everywhere (base_values for the gradient kernels,
+// fast_value_at_c for every K-build path), so every path writes the same bits: iu = 1 / (2 a l^2) once per
+// thread, then one multiply, one log1p, one multiply and one exp per element.  a is used as given: a <= 0 gives
+// IEEE NaN / inf (gpk.h).  Rounding: u carries <= 3 eps relative, so the exponent a log1p(u) carries
+// <= ~4 eps a log1p(u) absolute, which is the relative error of k.
+__device__ __forceinline__ double rq_iu(double l, double a) {
+#pragma clang fp contract(on)
+  return 1.0 / ((2.0 * a) * (l * l));
+}
+__device__ __forceinline__ double rq_value(double s, double iu, double a) {
+#pragma clang fp contract(on)
+  const double u = s * iu;
+  return exp(-a * log1p(u));
+}
+
+// g(u) = u / (1 + u) - log1p(u) = d log k / d a, u >= 0.  The two terms cancel: g = -u^2 / 2 + O(u^3), and the
+// direct form's relative error is ~ 2 eps / u.  With w = u / (1 + u), log1p(u) = -log(1 - w), so
+// g = -sum_{k >= 2} w^k / k: below RQ_G_SERIES_U the series to w^10 (truncation <= (2 / 11) w^9 relative, 1e-17 at
+// the threshold), above it the direct form (2 eps / u <= 3e-14 there).  Measured against mpmath: DESIGN 16.
+constexpr double RQ_G_SERIES_U = 0.015625;  // 2^-6
+__device__ __forceinline__ double rq_g(double u) {
+#pragma clang fp contract(on)
+  const double w = u / (1.0 + u);
+  if (u < RQ_G_SERIES_U) {
+    double p = 1.0 / 10.0;
+    p = fma(p, w, 1.0 / 9.0);
+    p = fma(p, w, 1.0 / 8.0);
+    p = fma(p, w, 1.0 / 7.0);
+    p = fma(p, w, 1.0 / 6.0);
+    p = fma(p, w, 1.0 / 5.0);
+    p = fma(p, w, 1.0 / 4.0);
+    p = fma(p, w, 1.0 / 3.0);
+    p = fma(p, w, 0.5);
+    return -(w * w) * p;
+  }
+  return w - log1p(u);
+}
+
+// number of rational quadratic leaves of a program: one or more selects the instantiations that carry the leaf's
+// code (template parameter RQL of the evaluators below; launch_assemble, launch_grad, launch_vjp).  log1p on top of
+// exp costs registers -- 127 -> 171 VGPRs in the single-node K build, four waves per SIMD down to two -- so the
+// kernels every other program runs compile none of it and are, instruction for instruction, what they were before the
+// leaf existed.  Every evaluation of a program goes through one of those three launches (or the fused first trailing
+// update, single SE / MAT32 / MAT52 nodes only), so an instantiation without the code never sees an RQ node.
+__host__ __device__ inline int rq_leaves(const gpk_kdesc& kd) {
+  int nr = 0;
+  for (int q = 0; q < kd.n_nodes; ++q) nr += kd.nodes[q].op == GPK_OP_RQ ? 1 : 0;
+  return nr;
+}
+
 // Values of one base node for R row points a[i] against one column point b.  The R evaluations
 // are independent, so the compiler interleaves their long f64 chains (exp / sin / sqrt / div).
-template <int R>
+template <int R, bool RQL = false>
 __device__ __forceinline__ void base_values(const gpk_node& nd, const double* __restrict__ hyp,
                                             const double* const (&a)[R], const double* b, int d, double (&r)[R]) {
 #pragma clang fp contract(on)  // fuse within an expression only: every caller rounds alike
@@ -187,6 +239,23 @@ __device__ __forceinline__ void base_values(const gpk_node& nd, const double* __
       for (int i = 0; i < R; ++i) r[i] += (a[i][k] - ck) * tb;
     }
     sg_at = d;
+  } else if (RQL && nd.op == GPK_OP_RQ) {  // (1 + s / (2 a l^2))^(-a): SE's direct sum of squares, then rq_value
+    double s[R];
+#pragma unroll
+    for (int i = 0; i < R; ++i) s[i] = 0.0;
+    for (int k = 0; k < d; ++k) {
+      const double bk = b[k];
+#pragma unroll
+      for (int i = 0; i < R; ++i) {
+        const double t = a[i][k] - bk;
+        s[i] += t * t;
+      }
+    }
+    const double av = h[1];
+    const double iu = rq_iu(h[0], av);
+#pragma unroll
+    for (int i = 0; i < R; ++i) r[i] = rq_value(s[i], iu, av);
+    sg_at = 2;
   } else if (nd.op == GPK_OP_CPW) {  // w(a) w(b): the direct form (the K build multiplies the staged w's: same bits)
     const double wb = cp_window(fl, h, b[0]);
 #pragma unroll
@@ -236,11 +305,12 @@ __device__ __forceinline__ void base_values(const gpk_node& nd, const double* __
   }
 }
 
+template <bool RQL = false>
 __device__ __forceinline__ double base_value(const gpk_node& nd, const double* __restrict__ hyp,
                                              const double* a, const double* b, int d) {
   const double* aa[1] = {a};
   double r[1];
-  base_values<1>(nd, hyp, aa, b, d, r);
+  base_values<1, RQL>(nd, hyp, aa, b, d, r);
   return r[0];
 }
 
@@ -296,6 +366,9 @@ __device__ __forceinline__ int fast_off(const gpk_kdesc& kd, int slot_stride) {
   return (kd.nodes[0].flags & GPK_NODE_ARD) ? (kd.nodes[0].ard_slot + 1) * slot_stride : 0;
 }
 
+// (RQL: as the evaluators' -- the instantiations never launched on a program with a rational quadratic leaf carry none
+// of its code, here its two constants)
+template <bool RQL = false>
 __device__ __forceinline__ FastNode make_fast_node(const gpk_node& nd, const double* hyp, int d) {
   FastNode f;
   f.op = nd.op;
@@ -315,13 +388,18 @@ __device__ __forceinline__ FastNode make_fast_node(const gpk_node& nd, const dou
     f.c = h;
     f.iper = 0.0;
     sg_at = d;
+  } else if (RQL && nd.op == GPK_OP_RQ) {  // hyp [l, a, (sg)]: a in iper (free for every node but PER), il2 set below
+    l = h[0];
+    f.iper = h[1];
+    sg_at = 2;
   } else {  // (a window leaf, GPK_OP_CPW, lands here too: it uses none of these constants)
     l = ard ? 1.0 : (nd.op == GPK_OP_SE ? h[0] : fabs(h[0]));
     f.iper = 0.0;
     sg_at = ard ? d : 1;
   }
   f.il = 1.0 / l;
-  f.il2 = 1.0 / (l * l);
+  // (a rational quadratic node keeps 1 / (2 a l^2) here: u = s * il2, rq_value)
+  f.il2 = (RQL && nd.op == GPK_OP_RQ) ? rq_iu(l, f.iper) : 1.0 / (l * l);
   f.i3l2 = 1.0 / (3.0 * (l * l));
   f.sg = (nd.flags & GPK_NODE_SCALED) ? h[sg_at] : 1.0;
   f.sc = 0;
@@ -377,7 +455,7 @@ __device__ __forceinline__ double sin2_pi(double t) {
 
 // fast_value over coordinate accessors: a(k), b(k) return coordinate k of the two points, c(k) offset k of a
 // linear node (read by that node only: callers that hold the offsets in registers pass them here)
-template <typename PA, typename PB, typename PC>
+template <bool RQL = false, typename PA, typename PB, typename PC>
 __device__ __forceinline__ double fast_value_at_c(const FastNode& f, PA a, PB b, PC c) {
 #pragma clang fp contract(on)  // fuse within an expression only: every caller rounds alike
   const int d = f.d;
@@ -416,6 +494,14 @@ __device__ __forceinline__ double fast_value_at_c(const FastNode& f, PA a, PB b,
     // c in registers, (b_k - c_k) is invariant over the lane's rows: hoisting it is left to the compiler
     r = 0.0;
     for (int k = 0; k < d; ++k) r += (a(k) - c(k)) * (b(k) - c(k));
+  } else if (RQL && f.op == GPK_OP_RQ) {
+    // SE's direct sum of squares, then the shared rq_value (il2 = 1 / (2 a l^2), iper = a: make_fast_node)
+    double s = 0.0;
+    for (int k = 0; k < d; ++k) {
+      const double t = a(k) - b(k);
+      s += t * t;
+    }
+    r = rq_value(s, f.il2, f.iper);
   } else {
     double dist = 0.0;
     if (f.flags & GPK_NODE_STANDARD) {
@@ -438,19 +524,20 @@ __device__ __forceinline__ double fast_value_at_c(const FastNode& f, PA a, PB b,
   return f.sg * r;
 }
 
-template <typename PA, typename PB>
+template <bool RQL = false, typename PA, typename PB>
 __device__ __forceinline__ double fast_value_at(const FastNode& f, PA a, PB b) {
   const double* cc = f.c;
-  return fast_value_at_c(f, a, b, [cc](int k) { return cc[k]; });
+  return fast_value_at_c<RQL>(f, a, b, [cc](int k) { return cc[k]; });
 }
 
+template <bool RQL = false>
 __device__ __forceinline__ double fast_value(const FastNode& f, const double* a, const double* b, bool sc_on = false) {
   if (sc_on && f.sc && f.op == GPK_OP_PER) {
     const int so = f.sc_sin, co = f.sc_cos;
     return per_sc_value(f, [a, so](int k) { return a[so + k]; }, [a, co](int k) { return a[co + k]; },
                         [b, so](int k) { return b[so + k]; }, [b, co](int k) { return b[co + k]; });
   }
-  return fast_value_at(f, [a](int k) { return a[k]; }, [b](int k) { return b[k]; });
+  return fast_value_at<RQL>(f, [a](int k) { return a[k]; }, [b](int k) { return b[k]; });
 }
 
 // The postfix program with every base node's constants precomputed (fns[q] = make_fast_node of
@@ -459,7 +546,8 @@ __device__ __forceinline__ double fast_value(const FastNode& f, const double* a,
 // change-point window leaves; the others carry none of this code): a window leaf's value is the product of its two
 // staged w's (the point slot fns[q].off) -- one multiply per element; cp_zero: bit q set -- window leaf q is exactly
 // zero on this tile (workgroup-uniform): +0.0 stands for (window, sibling, MUL) where the node has a skip_to.
-template <bool WIN = false>
+// RQL: the instantiation for programs with rational quadratic leaves (rq_leaves).
+template <bool WIN = false, bool RQL = false>
 __device__ __forceinline__ double eval_tree_fast(const gpk_kdesc& kd, const FastNode* fns, const double* pa,
                                                  const double* pb, bool sc_on = false, unsigned cp_zero = 0u) {
   Stack st;
@@ -485,7 +573,7 @@ __device__ __forceinline__ double eval_tree_fast(const gpk_kdesc& kd, const Fast
       sp += 1;
     } else {
       const FastNode f = fns[q];
-      st.set(sp, fast_value(f, pa + f.off, pb + f.off, sc_on));
+      st.set(sp, fast_value<RQL>(f, pa + f.off, pb + f.off, sc_on));
       sp += 1;
     }
   }

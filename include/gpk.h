@@ -68,6 +68,11 @@ enum { GPK_F64 = 0, GPK_F32 = 1 };
 enum {
   GPK_OP_LIN = 102, /* sum_k (x_k - c_k)(y_k - c_k) (KernelBasics/BaseKernels.py:114-134): hyp [c_0..c_{dim-1}, (sg)];
                        flags GPK_NODE_SCALED or 0 only (no ARD, expanded or standard form), ard_slot -1 */
+  GPK_OP_RQ = 103,  /* rational quadratic, sg (1 + u)^(-a) with u = s / (2 a l^2), s = sum_k (x_k - y_k)^2 (the standard
+                       definition; the reference names RQ = 103 and defines no formula): hyp [l, a, (sg)], the slot layout
+                       of GPK_OP_PER.  flags GPK_NODE_SCALED or 0 only (no ARD, expanded or standard form), ard_slot -1.
+                       `a` is used as given (no fabs): a <= 0 gives IEEE NaN / inf in K, which the factorisation reports
+                       through `info` like any matrix that is not positive definite */
   GPK_OP_PER = 104,
   GPK_OP_SE = 105,
   GPK_OP_MAT32 = 107,
@@ -202,7 +207,8 @@ int gpk_nlml(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_dev,
  *   1/2 sum_ij ((K^-1)_ij - alpha_i alpha_j) dK_ij/d theta  -- the derivative the reference takes by
  *   tf.GradientTape through LogLikelihood.get_metric (Optimizer/Fitter.py:104-158).
  * grad_dev may be NULL (then only -LML and the inverse, e.g. for get_K_inv); NaN where info != 0.
- * work: device scratch of gpk_grad_workspace_bytes(kd, lay) bytes. */
+ * work: device scratch of gpk_grad_workspace_bytes(kd, lay) bytes (0 for a kernel program that is not valid for
+ * the layout's dimension -- gpk_nlml_grad refuses it). */
 size_t gpk_grad_workspace_bytes(const gpk_kdesc* kd, const gpk_layout* lay);
 int gpk_nlml_grad(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_dev, int64_t hyp_stride,
                   const double* noise_dev, int64_t noise_stride, const double* X, int64_t x_bstride,

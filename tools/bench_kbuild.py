@@ -2,12 +2,14 @@
 tiles written, and element rate, for the SURVEY configs whose K build is not fused into the first
 trailing update.
 
-usage: python tools/bench_kbuild.py [case ...]   (cases: C5, C3, SE8192, LIN, CP; default C5 C3 SE8192)
+usage: python tools/bench_kbuild.py [case ...]   (cases: C5, C3, SE8192, LIN, RQ, CP; default C5 C3 SE8192)
 C5: ADD(SE-ARD, PER standard) D=8, N=16384 fp64; C3: MAT52-ARD D=4, N=8192 fp32; SE8192: SE D=1, N=8192
-fp64 batch 32 (the metric's inputs, built unfused).  Median of 10 launches, HIP events on the stream.
+fp64 batch 32 (the metric's inputs, built unfused).  Median, min and max of 10 launches, HIP events on the stream.
 LIN: the single-node LIN build against the single-node SE build through the same plain assemble launch, N = 8192,
 D = 1 and D = 8, fp64 and fp32 out (gpk_tune asm_f32_fast 0 for both, so SE's f32 build takes the same path): the
 two kernels alternate inside one run, 20 samples of 10 launches each; median, min and max (the run's own spread).
+RQ: the single-node RQ build against the single-node SE build by LIN's method, fp64 only (RQ programs have their own
+instantiation of the assemble kernel, SE takes the single-node one: both through the plain assemble launch).
 CP: the change-point device program (run_cp), same method.
 """
 import ctypes
@@ -66,20 +68,23 @@ def run(case):
     es = 4 if dtype == torch.float32 else 8
     lower = batch * lay.p * (lay.p + 64) / 2
     return {"case": case, "n": n, "d": d, "batch": batch, "kernel": kname, "dtype": dtn, "ms": round(ms, 3),
-            "GBps_lower_tiles": round(lower * es / (ms * 1e-3) / 1e9, 1),
+            "ms_min": round(min(ts), 3), "ms_max": round(max(ts), 3), "GBps_lower_tiles": round(lower * es / (ms * 1e-3) / 1e9, 1),
             "Gelem_per_s": round(batch * n * (n + 1) / 2 / (ms * 1e-3) / 1e9, 2), "w0": digest}
 
 
-def run_leaves(n=8192, samples=20, inner=10):
-    """Rows for SE and LIN (one node each) at D = 1 / 8, fp64 / fp32 out, alternating inside each sample."""
+def run_leaves(case="LIN", n=8192, samples=20, inner=10):
+    """Rows for SE and the leaf ``case`` (LIN or RQ; one node each) at D = 1 / 8, fp64 / fp32 out (RQ: fp64 only),
+    alternating inside each sample."""
     from gaussianprocessfundamentals_amd.KernelBasics import BaseKernels as bk
+    leaf = {"LIN": bk.LinearKernel, "RQ": bk.RationalQuadraticKernel}[case]
+    dtypes = ((torch.float64, "f64"), (torch.float32, "f32")) if case == "LIN" else ((torch.float64, "f64"),)
     dev = torch.device("cuda", 0)
     L = nat.lib()
     s = nat.stream_handle(dev)
     rows = []
     old = nat.tune("asm_f32_fast", 0)
     try:
-        for dtype, dtn in ((torch.float64, "f64"), (torch.float32, "f32")):
+        for dtype, dtn in dtypes:
             for d in (1, 8):
                 g = torch.Generator().manual_seed(7)
                 X = torch.rand(n, d, generator=g, dtype=torch.float64).to(dev).contiguous()
@@ -88,7 +93,7 @@ def run_leaves(n=8192, samples=20, inner=10):
                 f = engine.AugmentedFactorization(n, d, 0, 1, dtype)
                 lay = f.layout
                 progs = {}
-                for name, kern in (("SE", bk.SquaredExponentialKernel(d)), ("LIN", bk.LinearKernel(d))):
+                for name, kern in (("SE", bk.SquaredExponentialKernel(d)), (case, leaf(d))):
                     kd = engine.kernel_descriptor(kern, d)
                     H = (0.3 + torch.rand(1, kd.n_hyp, generator=g, dtype=torch.float64)).to(dev).contiguous()
                     progs[name] = (kd, H)
@@ -117,7 +122,7 @@ def run_leaves(n=8192, samples=20, inner=10):
                 lower = lay.p * (lay.p + 64) / 2
                 for name in progs:
                     ms = statistics.median(ts[name])
-                    rows.append({"case": "LIN", "kernel": name, "n": n, "d": d, "dtype": dtn, "ms": round(ms, 4),
+                    rows.append({"case": case, "kernel": name, "n": n, "d": d, "dtype": dtn, "ms": round(ms, 4),
                                  "ms_min": round(min(ts[name]), 4), "ms_max": round(max(ts[name]), 4),
                                  "GBps_lower_tiles": round(lower * es / (ms * 1e-3) / 1e9, 1)})
     finally:
@@ -202,8 +207,8 @@ if __name__ == "__main__":
         if c == "CP":
             for row in run_cp():
                 print(json.dumps(row), flush=True)
-        elif c == "LIN":
-            for row in run_leaves():
+        elif c in ("LIN", "RQ"):
+            for row in run_leaves(c):
                 print(json.dumps(row), flush=True)
         else:
             print(json.dumps(run(c)), flush=True)

@@ -126,12 +126,10 @@ class AbstractDataInput:
     def _detrend(self, x, y):
         if isinstance(self.mean_function, bmf.ZeroMeanFunction):
             return y
+        # y - m(x) in one device call (gpk_mean_eval with the targets), every member of a batch included
+        from ..engine import mean_vector
         mf = self.mean_function
-        if self.is_batch():
-            means = torch.stack([mf.get_tf_tensor(mf.get_last_hyper_parameter(), xb).reshape(-1, 1) for xb in x])
-        else:
-            means = mf.get_tf_tensor(mf.get_last_hyper_parameter(), x).reshape(-1, 1)
-        return y - means
+        return mean_vector(mf, mf.get_last_hyper_parameter(), x, y).reshape(y.shape)
 
     def get_detrended_y_train(self):
         """y - m(X) (DataInput.py:244-264); the zero mean returns y itself."""
@@ -156,8 +154,9 @@ class AbstractDataInput:
         y = _f64(data_y_test)
         if isinstance(self.mean_function, bmf.ZeroMeanFunction):
             return y
+        from ..engine import mean_vector
         mf = self.mean_function
-        return y - mf.get_tf_tensor(mf.get_last_hyper_parameter(), _f64(data_x_test)).reshape(-1, 1)
+        return mean_vector(mf, mf.get_last_hyper_parameter(), _f64(data_x_test), y).reshape(-1, 1)
 
     def get_independent_smoothed_grid_subset(self, subset_size: int, smoothing_kernel=None):
         """Declared without a body in the reference (AbstractDataInput.py:138-139): None."""

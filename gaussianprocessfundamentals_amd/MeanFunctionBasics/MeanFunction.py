@@ -22,6 +22,11 @@ class MeanFunction(bgpc.Component):
     def get_tf_tensor(self, hyper_parameter: List, x_vector):
         raise NotImplementedError
 
+    def _emit(self, nodes: list, offset: int, dim: int) -> int:
+        """Append the subtree's postfix nodes (op, hyp_offset, -1, 0) of the device mean program (include/gpk.h,
+        gpk_mdesc); returns the offset behind its flat hyperparameters."""
+        raise NotImplementedError("%s has no device form" % type(self).__name__)
+
     def get_mean_function_type(self):
         return self.type
 

@@ -117,18 +117,31 @@ class LogLikelihood(AbstractLogLikelihood):
         agg = global_param.p_batch_metric_aggregator or torch.mean
         return -agg(T)
 
-    def get_metric_and_gradient(self, hyper_parameter: List, noise, reset: bool = True):
+    def get_metric_and_gradient(self, hyper_parameter: List, noise, reset: bool = True,
+                                mean_hyper_parameter: List = None):
         """(-LML [1, 1], [d(-LML)/d h for h in hyper_parameter] (each shaped like h), d(-LML)/d noise).
 
         One device factorisation with identity extra rows yields K^-1 and alpha; one fused pass
         over the lower triangle evaluates 1/2 sum_ij ((K^-1)_ij - alpha_i alpha_j) dK_ij/d theta
         for every hyperparameter (gpk_nlml_grad).  This is the gradient the reference obtains by
         tf.GradientTape through get_metric (Optimizer/Fitter.py:104-158).  Gradients are NaN when
-        K + noise I is not positive definite (the metric is +inf)."""
+        K + noise I is not positive definite (the metric is +inf).
+
+        With ``mean_hyper_parameter`` (a hyperparameter list of the data input's mean function) the targets are
+        detrended on the device with those values (gpk_mean_eval) and a fourth element follows:
+        [d(-LML)/d h for h in mean_hyper_parameter] = -alpha^T dm/dh, by gpk_mean_vjp on the -alpha row the same
+        factorisation leaves in W.  DataInput with the Cholesky handling only."""
         if reset:
             self.covariance_matrix.reset()
             self.last_covariance_matrix = None
         H = mht.NumericalMatrixHandlingType
+        if mean_hyper_parameter is not None:
+            if self.data_input.data_x_train.dim() == 3:
+                raise NotImplementedError("mean-hyperparameter gradients are provided for DataInput, not BatchDataInput")
+            if self.local_approx in _MATRIX_APPROX or self.numerical_matrix_handling is not H.CHOLESKY_BASED:
+                raise NotImplementedError("mean-hyperparameter gradients are provided for the exact, Cholesky-based "
+                                          "likelihood")
+            return self._mean_metric_and_gradient(hyper_parameter, noise, mean_hyper_parameter)
         if self.local_approx in _MATRIX_APPROX and not (self.local_approx is mht.MatrixApproximations.SKI and
                                                         self.numerical_matrix_handling is H.CHOLESKY_BASED):
             raise NotImplementedError("approximate metrics: differentiate get_metric(hyper_parameter, noise, "
@@ -145,6 +158,20 @@ class LogLikelihood(AbstractLogLikelihood):
         f = self.covariance_matrix.inverse_factorization(hyper_parameter, noise, gradient=True)
         g = f.gradient()[0]   # (fresh buffers per evaluation: no copies needed)
         return f.nlml().reshape(1, 1), _split_like(g[:-1], hyper_parameter), g[-1]
+
+    def _mean_metric_and_gradient(self, hyper_parameter: List, noise, mean_hyper_parameter: List):
+        """get_metric_and_gradient on targets detrended with ``mean_hyper_parameter``, plus the mean gradient:
+        -LML = 1/2 (y - m)^T K^-1 (y - m) + ..., so d(-LML)/d theta_m = -alpha^T dm/d theta_m -- gpk_mean_vjp with
+        the weights read in place from the -alpha row of the identity-augmented W."""
+        from .. import engine
+        di = self.data_input
+        mean_function = di.mean_function
+        y = engine.mean_vector(mean_function, mean_hyper_parameter, di.data_x_train, di.data_y_train)
+        f = self.covariance_matrix.inverse_factorization(hyper_parameter, noise, gradient=True, y=y)
+        g = f.gradient()[0]
+        gm = engine.mean_vjp(mean_function, mean_hyper_parameter, di.data_x_train, f.neg_alpha_rows())[0]
+        return (f.nlml().reshape(1, 1), _split_like(g[:-1], hyper_parameter), g[-1],
+                _split_like(gm, mean_hyper_parameter))
 
     def _batch_metric_and_gradient(self, hyper_parameter: List, noise):
         """BatchDataInput (quirk Q7).  CHOLESKY_BASED: -LML = -agg_b(-1/2 fit_b - 1/2 sum_b' logdet_b' - c):

@@ -182,15 +182,19 @@ class HolisticCovarianceMatrix(CovarianceMatrix):
             self._inv_fact.check_info()
         return self._inv_fact
 
-    def inverse_factorization(self, hyper_parameter, noise, gradient: bool = True, y_scale: float = 1.0):
+    def inverse_factorization(self, hyper_parameter, noise, gradient: bool = True, y_scale: float = 1.0, y=None):
         """One factorisation with identity extra rows (engine.InverseFactorization): -LML, K^-1,
         L^-1, alpha and (gradient=True) d(-LML)/d(hyperparameters, noise) for every member of a
         DataInput (batch 1) or BatchDataInput (one member per batch entry).  y_scale multiplies the
-        targets (the batch aggregate's gradient weights the data fit by 1 / B).  Not memoised."""
+        targets (the batch aggregate's gradient weights the data fit by 1 / B); ``y`` replaces the data input's
+        detrended targets (targets detrended with other mean hyperparameters).  Not memoised."""
         self._require_data()
         if not _is_scalar(noise):
             raise Exception("No Data Input given or Noise unspecified")
-        x, y = self._xy()
+        if y is None:
+            x, y = self._xy()
+        else:
+            x, y = self.data_input.data_x_train, engine.as_device_f64(y)
         batch, n, d = self._shape(x)
         kd = engine.kernel_descriptor(self.kernel, d)
         hyp, nz = engine.pack_hyper_parameter_and_noise(hyper_parameter, noise, kd.n_hyp)

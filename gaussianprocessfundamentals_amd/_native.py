@@ -19,6 +19,9 @@ GPK_F64, GPK_F32 = 0, 1
 OP_LIN, OP_PER, OP_SE, OP_MAT32, OP_MAT52, OP_ADD, OP_MUL = 102, 104, 105, 107, 108, 201, 202
 OP_RQ = 103   # rational quadratic leaf (1 + s / (2 a l^2))^(-a), hyp [l, a, (sg)]
 OP_CPW = 203  # change-point window leaf w(x) w(y) (the value of KernelManifestation.CP)
+# mean-program ops (include/gpk.h GPK_MOP_*: the values of MeanFunctionManifestation)
+MOP_C, MOP_LIN, MOP_EXP, MOP_LOGIT, MOP_ADD, MOP_MUL = 101, 102, 103, 104, 201, 202
+MEAN_POINTS_PER_WG = 256  # GPK_MEAN_POINTS_PER_WG: points per workgroup of the mean kernels
 NODE_SCALED, NODE_ARD, NODE_SE_EXPANDED, NODE_STANDARD = 1, 2, 4, 8
 NODE_CP_LO, NODE_CP_HI, NODE_CP_SIGMOID, NODE_CP_APPROX = 16, 32, 64, 128
 MAX_NODES, MAX_DIM, MAX_ARD, MAX_HYP = 16, 16, 2, 64
@@ -37,7 +40,7 @@ EXPORTS = (
     "gpk_ski_weights", "gpk_add_diagonal", "gpk_distance_matrix", "gpk_workspace_bytes", "gpk_nlml_batched", "gpk_potrf_lower", "gpk_trsv_lower", "gpk_posterior",
     "gpk_kernel_vjp_workspace_bytes", "gpk_kernel_vjp", "gpk_pinv_backward_scale", "gpk_syevd_workspace_bytes",
     "gpk_syevd", "gpk_chain_plan", "gpk_tune_thread", "gpk_chain_stats", "gpk_chain_plan_ex",
-    "gpk_op_supported",
+    "gpk_op_supported", "gpk_mean_op_supported", "gpk_mean_eval", "gpk_mean_vjp_workspace_bytes", "gpk_mean_vjp",
 )
 
 
@@ -55,6 +58,11 @@ class GpkNode(ctypes.Structure):
 
 class GpkKdesc(ctypes.Structure):
     _fields_ = [("n_nodes", c_int32), ("n_hyp", c_int32), ("dim", c_int32), ("n_ard", c_int32),
+                ("nodes", GpkNode * MAX_NODES)]
+
+
+class GpkMdesc(ctypes.Structure):
+    _fields_ = [("n_nodes", c_int32), ("n_hyp", c_int32), ("dim", c_int32), ("reserved", c_int32),
                 ("nodes", GpkNode * MAX_NODES)]
 
 
@@ -133,10 +141,16 @@ def _declare(lib):
         "gpk_kernel_vjp": (c_int, [POINTER(GpkKdesc), P, P, c_int64, P, c_int64, c_int32, P, c_int64, P, P, P, P,
                                    P, c_size_t, P]),
         "gpk_op_supported": (c_int, [c_int32]),
+        "gpk_mean_op_supported": (c_int, [c_int32]),
+        "gpk_mean_eval": (c_int, [POINTER(GpkMdesc), P, c_int64, P, c_int64, c_int64, c_int32, P, c_int64, P, c_int64,
+                                  P]),
+        "gpk_mean_vjp_workspace_bytes": (c_size_t, [POINTER(GpkMdesc), c_int64, c_int32]),
+        "gpk_mean_vjp": (c_int, [POINTER(GpkMdesc), P, c_int64, P, c_int64, c_int64, c_int32, P, c_int64, P, P,
+                                 c_size_t, P]),
     }
     for name, (res, args) in sig.items():
-        if name == "gpk_op_supported" and not hasattr(lib, name):
-            continue  # (a library built before the entry existed -- same ABI number: op_supported() then says no)
+        if (name == "gpk_op_supported" or name.startswith("gpk_mean_")) and not hasattr(lib, name):
+            continue  # (a library built before the entry existed -- same ABI number: *op_supported() then says no)
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -170,6 +184,13 @@ def op_supported(op: int) -> bool:
     """Whether the loaded libgpk evaluates kernel-program op ``op`` (gpk_op_supported; host only).  A library built
     before the entry existed counts as supporting none of the ops added since."""
     fn = getattr(load_library(), "gpk_op_supported", None)
+    return bool(fn is not None and fn(int(op)) == 1)
+
+
+def mean_op_supported(op: int) -> bool:
+    """Whether the loaded libgpk evaluates mean-program op ``op`` (gpk_mean_op_supported; host only); False for a
+    library built before the mean programs existed."""
+    fn = getattr(load_library(), "gpk_mean_op_supported", None)
     return bool(fn is not None and fn(int(op)) == 1)
 
 

@@ -2225,6 +2225,74 @@ int gpk_kernel_vjp(const gpk_kdesc* kd, const double* hyp_dev, const double* X, 
   return 0;
 }
 
+int gpk_mean_op_supported(int32_t op) {
+  return (mean_leaf_hyp(op, 1) > 0 || op == GPK_MOP_ADD || op == GPK_MOP_MUL) ? 1 : 0;
+}
+
+// the checks gpk_mean_eval and gpk_mean_vjp share (arguments 1 .. 7 of both)
+static int check_mean_call(const gpk_mdesc* md, const double* hyp_dev, int64_t hyp_stride, const double* X, int64_t n,
+                           int64_t x_bstride, int32_t batch) {
+  if (const char* why = mean_desc_error(md)) return fail_arg(1, why);
+  if (!hyp_dev && md->n_hyp > 0) return fail_arg(2, "hyp_dev");
+  if (hyp_stride < 0) return fail_arg(3, "hyp_stride");
+  if (!X) return fail_arg(4, "X");
+  if (n < 1) return fail_arg(5, "n must be >= 1");
+  if (x_bstride < 0) return fail_arg(6, "x_bstride");
+  if (batch < 1) return fail_arg(7, "batch must be >= 1");
+  if (mean_blocks(n) > (int64_t)0x7fffffff / batch) return fail_arg(5, "n x batch: too many workgroups for one launch");
+  return 0;
+}
+
+int gpk_mean_eval(const gpk_mdesc* md, const double* hyp_dev, int64_t hyp_stride, const double* X, int64_t n,
+                  int64_t x_bstride, int32_t batch, const double* y, int64_t y_bstride, double* out,
+                  int64_t out_bstride, void* stream) {
+  if (int e = check_mean_call(md, hyp_dev, hyp_stride, X, n, x_bstride, batch)) return e;
+  if (y && y_bstride < 0) return fail_arg(9, "y_bstride");
+  if (!out) return fail_arg(10, "out");
+  if (out_bstride < (batch > 1 ? n : 0)) return fail_arg(11, "out_bstride");
+  MeanArgs a;
+  memset(&a, 0, sizeof(a));
+  a.hyp = hyp_dev;
+  a.hyp_stride = hyp_stride;
+  a.X = X;
+  a.x_bs = x_bstride;
+  a.n = n;
+  a.y = y;
+  a.y_bs = y_bstride;
+  a.out = out;
+  a.out_bs = out_bstride;
+  GPK_HIP(launch_mean_eval(*md, a, batch, reinterpret_cast<hipStream_t>(stream)), "mean_eval");
+  return 0;
+}
+
+size_t gpk_mean_vjp_workspace_bytes(const gpk_mdesc* md, int64_t n, int32_t batch) {
+  if (mean_desc_error(md) || n < 1 || batch < 1) return 0;
+  return (size_t)batch * (size_t)mean_blocks(n) * (size_t)std::max<int32_t>(1, md->n_hyp) * sizeof(double);
+}
+
+int gpk_mean_vjp(const gpk_mdesc* md, const double* hyp_dev, int64_t hyp_stride, const double* X, int64_t n,
+                 int64_t x_bstride, int32_t batch, const double* g, int64_t g_bstride, double* grad_hyp, void* work,
+                 size_t work_bytes, void* stream) {
+  if (int e = check_mean_call(md, hyp_dev, hyp_stride, X, n, x_bstride, batch)) return e;
+  if (!g) return fail_arg(8, "g");
+  if (g_bstride < 0) return fail_arg(9, "g_bstride");
+  if (!grad_hyp) return fail_arg(10, "grad_hyp");
+  if (!work || work_bytes < gpk_mean_vjp_workspace_bytes(md, n, batch))
+    return fail_arg(11, "work (see gpk_mean_vjp_workspace_bytes)");
+  MeanArgs a;
+  memset(&a, 0, sizeof(a));
+  a.hyp = hyp_dev;
+  a.hyp_stride = hyp_stride;
+  a.X = X;
+  a.x_bs = x_bstride;
+  a.n = n;
+  a.g = g;
+  a.g_bs = g_bstride;
+  a.part = static_cast<double*>(work);
+  GPK_HIP(launch_mean_vjp(*md, a, batch, grad_hyp, reinterpret_cast<hipStream_t>(stream)), "mean_vjp");
+  return 0;
+}
+
 int gpk_add_diagonal(double* A, int64_t n, int64_t lda, int64_t a_bstride, int32_t batch, double value,
                      void* stream) {
   if (!A && n > 0) return fail_arg(1, "A");

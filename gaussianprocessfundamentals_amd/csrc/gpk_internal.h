@@ -347,6 +347,34 @@ hipError_t launch_distance(int mode, const double* A, int64_t n, int64_t a_bs, c
 hipError_t launch_add_diag(double* A, int64_t n, int64_t lda, int64_t a_bs, double value, int32_t batch,
                            hipStream_t s);
 
+// mean-function programs (gpk_mean.hip)
+struct MeanArgs {
+  const double* hyp;
+  int64_t hyp_stride;
+  const double* X;
+  int64_t x_bs;
+  int64_t n;
+  const double* y;  // eval: NULL = the mean itself, else the targets to detrend
+  int64_t y_bs;
+  double* out;      // eval
+  int64_t out_bs;
+  const double* g;  // vjp: per-point weights
+  int64_t g_bs;
+  double* part;     // vjp: [batch][nblk][n_hyp] per-workgroup partial sums
+  // set by the launchers
+  int64_t nblk;     // workgroups per member
+  int32_t n_nodes, n_hyp, d;
+  int32_t op[GPK_MAX_NODES];
+  int32_t off[GPK_MAX_NODES];
+  int32_t lhs[GPK_MAX_NODES];  // binary nodes: the nodes whose values they pop (below, top)
+  int32_t rhs[GPK_MAX_NODES];
+};
+const char* mean_desc_error(const gpk_mdesc* md);  // NULL for a valid program, else what is wrong with it
+int mean_leaf_hyp(int32_t op, int32_t dim);         // hyperparameters of a leaf op, -1 for anything else
+int64_t mean_blocks(int64_t n);                     // workgroups per member
+hipError_t launch_mean_eval(const gpk_mdesc& md, MeanArgs a, int32_t batch, hipStream_t s);
+hipError_t launch_mean_vjp(const gpk_mdesc& md, MeanArgs a, int32_t batch, double* grad, hipStream_t s);
+
 enum { GEMM_UPDATE = 0, GEMM_TRSM = 1 };
 
 }  // namespace gpk

@@ -180,6 +180,149 @@ def kernel_matrix(kernel, hyper_parameter, x, x_, diag_add: float = 0.0, lower: 
     return K
 
 
+# ----------------------------------------------------------------------------- mean programs
+def mean_descriptor(mean_function, dim: Optional[int] = None) -> nat.GpkMdesc:
+    """Flatten ``mean_function`` (a MeanFunction tree) to the postfix mean program of include/gpk.h."""
+    dim = int(dim if dim is not None else mean_function.input_dimensionality)
+    if not nat.mean_op_supported(nat.MOP_LIN):
+        raise nat.NativeUnavailable("this libgpk.so has no mean-function programs (stale build): rebuild it with "
+                                    "__graft_entry__.build()")
+    if dim < 1 or dim > nat.MAX_DIM:
+        raise ValueError("input dimensionality must be in [1, %d]" % nat.MAX_DIM)
+    nodes: List[tuple] = []
+    n_hyp = mean_function._emit(nodes, 0, dim)
+    if len(nodes) > nat.MAX_NODES:
+        raise ValueError("mean-function tree too large for the device program (%d > %d nodes)"
+                         % (len(nodes), nat.MAX_NODES))
+    if n_hyp > nat.MAX_HYP:
+        raise ValueError("too many mean hyperparameters (%d > %d)" % (n_hyp, nat.MAX_HYP))
+    md = nat.GpkMdesc()
+    md.n_nodes = len(nodes)
+    md.n_hyp = n_hyp
+    md.dim = dim
+    md.reserved = 0
+    for i, (op, off, slot, flags) in enumerate(nodes):
+        md.nodes[i].op = op
+        md.nodes[i].hyp_offset = off
+        md.nodes[i].ard_slot = slot
+        md.nodes[i].flags = flags
+    return md
+
+
+def _mean_operands(mean_function, hyper_parameter, x):
+    """(md, hyp, hyp_stride, X, x_bstride, n, batch or None): ``x`` [n, d] or [B, n, d]; ``hyper_parameter`` a
+    hyperparameter list / flat vector (shared by the members) or a [B, n_hyp] matrix (one row per member)."""
+    x = as_device_f64(x)
+    if x.dim() not in (2, 3):
+        raise ValueError("mean-function inputs must be [n, D] or [B, n, D]")
+    n, d = int(x.shape[-2]), int(x.shape[-1])
+    md = mean_descriptor(mean_function, d)
+    if isinstance(hyper_parameter, torch.Tensor) and hyper_parameter.dim() == 2:
+        hyp = hyper_parameter.detach().to(device=x.device, dtype=torch.float64).contiguous()
+        if hyp.shape[1] != md.n_hyp:
+            raise ValueError("hyperparameter rows have %d values, the mean function expects %d"
+                             % (hyp.shape[1], md.n_hyp))
+        hb = int(hyp.shape[0])
+    else:
+        hyp, hb = pack_hyper_parameter(hyper_parameter, md.n_hyp), None
+    xb = int(x.shape[0]) if x.dim() == 3 else None
+    if hb is not None and xb is not None and hb != xb:
+        raise ValueError("%d hyperparameter rows for %d input members" % (hb, xb))
+    batch = hb if hb is not None else xb
+    return md, hyp, (md.n_hyp if hb is not None else 0), x, (n * d if xb is not None else 0), n, batch
+
+
+def mean_vector(mean_function, hyper_parameter, x, y=None) -> torch.Tensor:
+    """m(x) -- or, with targets ``y``, the detrended targets y - m(x) -- by gpk_mean_eval: [n], or [B, n] when the
+    inputs ([B, n, d]), the hyperparameters ([B, n_hyp]) or the targets ([B, n] / [B, n, 1]) carry a batch.
+    The reference's MeanFunction.get_tf_tensor and DataInput.get_detrended_y_* (DataHandling/DataInput.py:244-264)."""
+    L = nat.lib()
+    md, hyp, hyp_stride, X, x_bstride, n, batch = _mean_operands(mean_function, hyper_parameter, x)
+    yv, y_bstride = None, 0
+    if y is not None:
+        yv = as_device_f64(y)
+        if yv.dim() >= 2 and yv.shape[-1] == 1 and yv.shape[-2] == n:
+            yv = yv.reshape(yv.shape[:-1])
+        if yv.dim() == 2:
+            if batch is not None and int(yv.shape[0]) != batch:
+                raise ValueError("%d target members for a batch of %d" % (yv.shape[0], batch))
+            batch, y_bstride = int(yv.shape[0]), n
+        if yv.dim() not in (1, 2) or int(yv.shape[-1]) != n:
+            raise ValueError("targets must hold %d values per member" % n)
+        yv = yv.contiguous()
+    B = batch or 1
+    out = torch.empty((B, n), dtype=torch.float64, device=X.device)
+    if n > 0:
+        nat.check(L.gpk_mean_eval(ctypes.byref(md), nat.ptr(hyp), hyp_stride, nat.ptr(X), n, x_bstride, B,
+                                  nat.ptr(yv), y_bstride, nat.ptr(out), n, nat.stream_handle(X.device)),
+                  "gpk_mean_eval")
+    return out if batch is not None else out[0]
+
+
+def mean_vjp(mean_function, hyper_parameter, x, g: torch.Tensor) -> torch.Tensor:
+    """sum_i g_i dm(x_i) / d(hyperparameters) by gpk_mean_vjp: the flat adjoint [n_hyp] (DFS order), or [B, n_hyp]
+    for batched operands (see :func:`mean_vector`; ``g`` [n] or [B, n]).  A float64 ``g`` whose rows are contiguous
+    is read where it lies, whatever its batch stride -- e.g. the -alpha rows of an identity-augmented factorisation
+    (:meth:`InverseFactorization.neg_alpha_rows`)."""
+    L = nat.lib()
+    md, hyp, hyp_stride, X, x_bstride, n, batch = _mean_operands(mean_function, hyper_parameter, x)
+    g = g.detach()
+    if g.dim() >= 2 and g.shape[-1] == 1 and g.shape[-2] == n:
+        g = g.reshape(g.shape[:-1])
+    if g.dim() not in (1, 2) or int(g.shape[-1]) != n:
+        raise ValueError("g must hold %d weights per member" % n)
+    if g.dim() == 2:
+        if batch is not None and int(g.shape[0]) != batch:
+            raise ValueError("%d weight members for a batch of %d" % (g.shape[0], batch))
+        batch = int(g.shape[0])
+    if g.dtype != torch.float64 or g.device != X.device or g.stride(-1) != 1 or (g.dim() == 2 and g.stride(0) < 0):
+        g = g.to(device=X.device, dtype=torch.float64).contiguous()
+    g_bstride = int(g.stride(0)) if g.dim() == 2 else 0
+    B = batch or 1
+    grad = torch.zeros((B, md.n_hyp), dtype=torch.float64, device=X.device)
+    if n > 0:
+        wb = int(L.gpk_mean_vjp_workspace_bytes(ctypes.byref(md), n, B))
+        work = torch.empty(max(1, (wb + 7) // 8), dtype=torch.float64, device=X.device)
+        nat.check(L.gpk_mean_vjp(ctypes.byref(md), nat.ptr(hyp), hyp_stride, nat.ptr(X), n, x_bstride, B, nat.ptr(g),
+                                 g_bstride, nat.ptr(grad), nat.ptr(work), wb, nat.stream_handle(X.device)),
+                  "gpk_mean_vjp")
+    return grad if batch is not None else grad[0]
+
+
+class _MeanValue(torch.autograd.Function):
+    """m(x) with the device reverse mode: autograd through a mean function's get_tf_tensor, as the reference's
+    tape differentiates it (Optimizer/Fitter.py:104-158)."""
+
+    @staticmethod
+    def forward(ctx, mean_function, x, *hyper_parameter):
+        ctx.mean_function, ctx.x = mean_function, x
+        ctx.like = [(h.shape, h.device, h.dtype) for h in hyper_parameter]
+        ctx.flat = pack_hyper_parameter([h.detach() for h in hyper_parameter])
+        return mean_vector(mean_function, ctx.flat, x)
+
+    @staticmethod
+    def backward(ctx, gout):
+        flat = mean_vjp(ctx.mean_function, ctx.flat, ctx.x, gout.contiguous())
+        grads, i = [], 0
+        for shape, dev, dt in ctx.like:
+            k = 1
+            for s in shape:
+                k *= int(s)
+            grads.append(flat[i:i + k].reshape(shape).to(device=dev, dtype=dt))
+            i += k
+        return (None, None) + tuple(grads)
+
+
+def mean_tensor(mean_function, hyper_parameter: Sequence, x) -> torch.Tensor:
+    """get_tf_tensor of the device mean functions: [n] fp64, differentiable in the hyperparameters when one of
+    them requires a gradient (the backward pass is gpk_mean_vjp)."""
+    hs = list(hyper_parameter)
+    if torch.is_grad_enabled() and any(isinstance(h, torch.Tensor) and h.requires_grad for h in hs):
+        return _MeanValue.apply(mean_function, x, *[h if isinstance(h, torch.Tensor)
+                                                    else torch.as_tensor(h, dtype=torch.float64) for h in hs])
+    return mean_vector(mean_function, hs, x)
+
+
 # ----------------------------------------------------------------------------- factorisation
 def _check_operand(name: str, t: torch.Tensor, bstride: int, per_member: int, batch: int,
                    dev: torch.device) -> None:
@@ -489,6 +632,12 @@ class InverseFactorization(AugmentedFactorization):
     def alpha(self, b: int = 0) -> torch.Tensor:
         lay = self.layout
         return -self.w(b)[lay.y_row, lay.n_pad:lay.n_pad + self.n].to(torch.float64)
+
+    def neg_alpha_rows(self) -> torch.Tensor:
+        """[batch, n] view of the -alpha rows inside W (element y_row * ld + n_pad of every member, batch stride
+        w_batch_stride): what gpk_mean_vjp reads in place for d(-LML)/d(mean hyperparameters)."""
+        lay = self.layout
+        return self.W.view(self.batch, lay.p, lay.ld)[:, lay.y_row, lay.n_pad:lay.n_pad + self.n]
 
 
 def _offset_ptr(t: torch.Tensor, elements: int):

@@ -31,7 +31,7 @@ def shard_range(n_items: int, rank: int, world: int) -> Tuple[int, int]:
 
 def native_batched_evaluator(kernel, X: torch.Tensor, y: torch.Tensor, noise, dtype=None,
                              max_batch: Optional[int] = None,
-                             pipeline: int = 1) -> Callable[[torch.Tensor], torch.Tensor]:
+                             pipeline: int = 1, mean_function=None) -> Callable[[torch.Tensor], torch.Tensor]:
     """Evaluator running gpk_assemble/gpk_potrf_aug/gpk_finalize over candidate batches.
 
     Candidates are factored in chunks of ``max_batch`` (all at once when None).  With
@@ -40,11 +40,16 @@ def native_batched_evaluator(kernel, X: torch.Tensor, y: torch.Tensor, noise, dt
     is then left to the pipelining: each chunk runs its kernels on its own stream).  The result is
     ordered on the caller's stream.
 
+    With a ``mean_function`` the candidate rows are [kernel hyperparameters | mean hyperparameters] (both flat, DFS
+    order): each chunk's targets are detrended per candidate by one gpk_mean_eval into a [b, n] buffer
+    (allocated on the chunk's stream), which the factorisation reads with a batch stride of n.
+
     Returns f(cands [c, n_hyp] fp64) -> [c, 2] fp64 device tensor of (nlml, info)."""
     X = engine.as_device_f64(X)
     yv = engine.as_device_f64(y).reshape(1, -1).contiguous()
     n, d = int(X.shape[0]), int(X.shape[1])
     kd = engine.kernel_descriptor(kernel, d)
+    n_mean = engine.mean_descriptor(mean_function, d).n_hyp if mean_function is not None else 0
     from .Statistics.CovarianceMatrix import noise_vector
     nv = noise_vector(noise)
     dt = dtype or gp.p_dtype
@@ -58,8 +63,12 @@ def native_batched_evaluator(kernel, X: torch.Tensor, y: torch.Tensor, noise, dt
         out = torch.empty((c, 2), dtype=torch.float64, device=X.device)
         if c == 0:
             return out
-        if cands.shape[1] != kd.n_hyp:
-            raise ValueError("candidate rows must have %d hyperparameter values" % kd.n_hyp)
+        if cands.shape[1] != kd.n_hyp + n_mean:
+            raise ValueError("candidate rows must have %d hyperparameter values" % (kd.n_hyp + n_mean))
+        if n_mean:
+            khyp, mhyp = cands[:, :kd.n_hyp].contiguous(), cands[:, kd.n_hyp:].contiguous()
+        else:
+            khyp = cands
         step = c if max_batch is None else max(1, int(max_batch))
         caller = torch.cuda.current_stream(X.device)
         slots = [caller] + streams
@@ -81,7 +90,13 @@ def native_batched_evaluator(kernel, X: torch.Tensor, y: torch.Tensor, noise, dt
                     f = engine.AugmentedFactorization(n, d, 0, b, dt)
                     cache[(b, slot)] = f
                 with torch.cuda.stream(slots[slot]):
-                    f.run(kd, cands[s0:s1], kd.n_hyp, nv, 0, X, 0, yv, 0)
+                    if n_mean:
+                        # (a fresh [b, n] buffer per chunk: the stream-ordered caching allocator keeps it until the
+                        # slot's stream has passed the factorisation that reads it)
+                        yd = engine.mean_vector(mean_function, mhyp[s0:s1], X, yv[0])
+                        f.run(kd, khyp[s0:s1], kd.n_hyp, nv, 0, X, 0, yd, n)
+                    else:
+                        f.run(kd, khyp[s0:s1], kd.n_hyp, nv, 0, X, 0, yv, 0)
                     out[s0:s1, 0] = f.nlml()
                     out[s0:s1, 1] = f.info.to(torch.float64)
         for st in streams:

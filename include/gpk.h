@@ -396,6 +396,67 @@ int gpk_kernel_vjp(const gpk_kdesc* kd, const double* hyp_dev, const double* X, 
 int gpk_add_diagonal(double* A, int64_t n, int64_t lda, int64_t a_bstride, int32_t batch, double value,
                      void* stream);
 
+/* ------------------------------------------------------------------------ mean-function programs
+ * The mean functions of the reference (MeanFunctionBasics/BaseMeanFunctions.py:37-193) and its mean-function
+ * operators (MeanFunctionBasics/Operators.py:117-184) as one postfix program over the points, in value
+ * (gpk_mean_eval: m(X), or the detrended targets y - m(X) of DataInput.get_detrended_y_*) and in reverse mode
+ * (gpk_mean_vjp: what the reference's tape gives the fitter for the mean hyperparameters).
+ * Op codes follow MeanFunctionManifestation (MeanFunctionBasics/MeanFunction.py:20-28); with d = dim and
+ * s = sum_k (a_k x_k - b_k), accumulated k = 0 .. d-1 by fused multiply-adds: */
+enum {
+  GPK_MOP_C = 101,     /* c                              hyp [c]                               */
+  GPK_MOP_LIN = 102,   /* sum_k a_k x_k                  hyp [a_0..a_{d-1}]                    */
+  GPK_MOP_EXP = 103,   /* base ^ s  (pow)                hyp [a_0..a_{d-1}, b_0..b_{d-1}, base] */
+  GPK_MOP_LOGIT = 104, /* c / (1 + exp(s))               hyp [a_0..a_{d-1}, b_0..b_{d-1}, c]    */
+  GPK_MOP_ADD = 201,   /* binary: pops two, pushes the sum (left fold of an n-ary operator)   */
+  GPK_MOP_MUL = 202    /* binary: pops two, pushes the product                                */
+};                     /* (MeanFunctionManifestation.CP = 203 has no class upstream: not an op) */
+/* Numerics.  Every value is used as given (no fabs): base <= 0 with a non-integer exponent gives IEEE NaN, as
+ * tf.pow does.  The partial derivatives the reverse mode uses:
+ *   EXP    d/da_k = m ln(base) x_k,  d/db_k = -m ln(base),  d/dbase = s base^(s-1)
+ *   LOGIT  d/da_k = -m sg(s) x_k,    d/db_k = m sg(s),      d/dc = 1 / (1 + exp(s)),   sg(s) = 1 / (1 + exp(-s))
+ * LOGIT's are evaluated in exactly this form -- two exponentials of opposite sign, each only ever in a denominator
+ * next to 1 -- so value and partials stay finite for every finite s (the quotient form -c e^s / (1 + e^s)^2 is
+ * inf / inf beyond s = 355): at s = 800 the value and every partial are 0, at s = -800 the value is c, d/dc is 1 and
+ * the others 0.
+ * The mean program: postfix like gpk_kdesc (children left to right, the binary op after each child beyond the
+ * first); hyperparameters flattened in the reference's DFS order, so leaf offsets are consecutive from 0 and add up
+ * to n_hyp.  In every node ard_slot is -1 and flags 0.  dim in [1, GPK_MAX_DIM], n_hyp <= GPK_MAX_HYP. */
+typedef struct {
+  int32_t n_nodes;
+  int32_t n_hyp;
+  int32_t dim;
+  int32_t reserved; /* 0 */
+  gpk_node nodes[GPK_MAX_NODES];
+} gpk_mdesc;
+
+/* 1 for every mean-program op (GPK_MOP_*) this library evaluates, else 0 (host only): the gpk_op_supported of the
+ * mean programs -- a binding asks here (and finds the symbol missing in a library built before it existed). */
+int gpk_mean_op_supported(int32_t op);
+
+/* out[b*out_bstride + i] = m(X[b][i]; hyp[b])  (y == NULL), or  y[b*y_bstride + i] - m(X[b][i]; hyp[b])  -- the
+ * detrended targets, one IEEE subtraction of the same m -- for i < n, b < batch.  X[b] = X + b*x_bstride is
+ * [n, dim] row-major; hyp[b] = hyp_dev + b*hyp_stride; a stride of 0 shares hyp, X or y between the members.
+ * Asynchronous on the stream.  -1: the program is not valid (stack discipline, per-op hyperparameter counts
+ * against dim and n_hyp, an unknown op, non-zero flags, dim out of range); -5 / -7: n < 1 / batch < 1. */
+int gpk_mean_eval(const gpk_mdesc* md, const double* hyp_dev, int64_t hyp_stride, const double* X, int64_t n,
+                  int64_t x_bstride, int32_t batch, const double* y, int64_t y_bstride, double* out,
+                  int64_t out_bstride, void* stream);
+
+/* Reverse mode: grad_hyp[b*n_hyp + p] = sum_i g[b*g_bstride + i] dm(X[b][i]; hyp[b]) / dhyp_p  (device
+ * [batch, n_hyp]).  g is contiguous within a member, so it may point into an identity-augmented factored W at
+ * element y_row*ld + n_pad with g_bstride = w_batch_stride -- the -alpha row gpk_nlml_grad leaves there -- and the
+ * result is then d(-LML)/d(mean hyperparameters), without a copy.  Deterministic: each workgroup of
+ * GPK_MEAN_POINTS_PER_WG points writes its partial sums (a fixed shuffle tree, then the waves in order) to the
+ * workspace and one ordered pass adds them up; no floating-point atomics, so two calls on the same inputs give the
+ * same bits.  work: gpk_mean_vjp_workspace_bytes(md, n, batch) bytes (host only; 0 for a program that is not valid
+ * or n < 1 or batch < 1 -- gpk_mean_vjp refuses those).  Errors as gpk_mean_eval. */
+#define GPK_MEAN_POINTS_PER_WG 256
+size_t gpk_mean_vjp_workspace_bytes(const gpk_mdesc* md, int64_t n, int32_t batch);
+int gpk_mean_vjp(const gpk_mdesc* md, const double* hyp_dev, int64_t hyp_stride, const double* X, int64_t n,
+                 int64_t x_bstride, int32_t batch, const double* g, int64_t g_bstride, double* grad_hyp, void* work,
+                 size_t work_bytes, void* stream);
+
 /* Per-kernel-class timing with HIP events recorded on the launch stream.
  * class: 0 assemble, 1 diag, 2 trsm, 3 update, 4 finalize, 5 trsv, 6 grad */
 #define GPK_NUM_CLASSES 7

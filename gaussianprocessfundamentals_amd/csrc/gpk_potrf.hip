@@ -104,6 +104,10 @@ __device__ __forceinline__ void glds16a(const void* src, void* lds_base) {
   __builtin_amdgcn_global_load_lds(src, (lds_void*)lds_base, 16, 0, AUX);
 }
 __device__ __forceinline__ int wave_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+// LDS byte address of a pointer into shared memory (what M0 holds for an LDS DMA)
+__device__ __forceinline__ unsigned lds_addr(const void* p) {
+  return (unsigned)(unsigned long)(lds_void*)const_cast<void*>(p);
+}
 
 // buffer loads / stores of one element (voffset per lane, soffset wave-uniform)
 template <typename T>
@@ -282,21 +286,38 @@ __global__ __launch_bounds__(128 * WN, (WN == 4 && MODE == GEMM_UPDATE) ? 4 : 2)
   const int wid = wave_uniform(tid >> 6);
   const int wr = wid / WN, wc = wid % WN;
 
+#ifndef GPK_UPD_PIPE
+#define GPK_UPD_PIPE 1  // 0: the plain K loop for the f64 128 x 128 update tile too (see GPK_PIPE_KLOOP)
+#endif
+  constexpr bool PIPE = GPK_UPD_PIPE && sizeof(T) == 8 && MODE == GEMM_UPDATE && TM == 128 && TN == 128 && WN == 4;
+  static_assert(!PIPE || PW == 4, "GPK_PIPE_GLDS_ASM issues four DMA instructions per wave");
   // per-lane source of each of this wave's glds instructions: rows [0, TM) are A, [TM, TM+TN) B
   const T* src[PW];
+  // PIPE: the same addresses as a wave-uniform base (the wave's PW x 8 rows are all A rows or all B rows) plus a
+  // 32-bit byte offset per lane (half the address registers; 128 rows of a matrix stay far below 4 GiB)
+  const T* const gsb = (wid * PW * 8 < TM) ? Ag : Bg;
+  uint32_t gso[PW];
 #pragma unroll
   for (int i = 0; i < PW; ++i) {
     const int g0 = (wid * PW + i) * 8;
     const int r = g0 + (lane >> 3);
-    if (g0 < TM)
+    if (g0 < TM) {
       src[i] = Ag + (int64_t)r * a.ld + swz(r, lane & 7) * EPC;
-    else
+      gso[i] = (uint32_t)(((int64_t)r * a.ld + swz(r, lane & 7) * EPC) * (int64_t)sizeof(T));
+    } else {
       src[i] = Bg + (int64_t)(r - TM) * ldb + swz(r - TM, lane & 7) * EPC;
+      gso[i] = (uint32_t)(((int64_t)(r - TM) * ldb + swz(r - TM, lane & 7) * EPC) * (int64_t)sizeof(T));
+    }
   }
 #define GPK_GLDS(stage, kc)                                                                   \
   {                                                                                           \
+    const char* gk_ = reinterpret_cast<const char*>(gsb + (int64_t)(kc) * GBK);               \
+    /* opaque, so that the chunk's base stays in SGPRs (saddr + 32-bit lane offset) instead of being folded into \
+       64-bit per-lane pointers */                                                           \
+    if constexpr (PIPE) asm volatile("" : "+s"(gk_));                                         \
     _Pragma("unroll") for (int i = 0; i < PW; ++i)                                            \
-        glds16(src[i] + (int64_t)(kc) * GBK, smem + (stage) * STAGE + (wid * PW + i) * 1024);   \
+        glds16(PIPE ? reinterpret_cast<const T*>(gk_ + gso[i]) : src[i] + (int64_t)(kc) * GBK, \
+               smem + (stage) * STAGE + (wid * PW + i) * 1024);                               \
   }
 
 #ifndef GPK_ABLATE_C
@@ -475,13 +496,133 @@ __global__ __launch_bounds__(128 * WN, (WN == 4 && MODE == GEMM_UPDATE) ? 4 : 2)
       GPK_GLDS(st ^ 1, (kc + 1) % NK0);                                                                  \
     }                                                                                                    \
   }
-  if (mact > 1) {
-    GPK_KLOOP(MB)
-  } else if (mact == 1) {
-    GPK_KLOOP(1)
-  } else {
-    GPK_KLOOP(0)
+  // Software-pipelined form of the loop for the f64 128 x 128 update tile (8 waves of 64 x 32: fragments a[4], b[2]
+  // per half h of a chunk; k-steps 2h, 2h + 1 use the half's pieces, elements 0 and 1).  The loop is rotated by one
+  // k-step: a wave carries the second-half pieces of chunk kc - 1 across the barrier and issues that chunk's last
+  // k-step (8 MFMAs, the "tail") behind the first fragment reads of chunk kc, so no wave leaves the barrier with an
+  // empty MFMA queue; every read is issued 4 to 16 MFMAs ahead of its first use, into registers whose previous value
+  // has just died, at fixed places (10 live fragment quads = 40 VGPRs at the peak, 24 in the plain loop; no copies):
+  //   barrier | R1 a0[0] b0[0] b0[1] a0[1] | DMA of chunk kc + 1 | tail m = 2, 3 | R2 a0[2] a0[3] | tail m = 0, 1
+  //   | R3 b1[0] b1[1] a1[0] a1[1] | k-steps 0, 1 of m = 0, 1 | k-steps 0, 1 of m = 2, 3 | R4 a1[2] a1[3]
+  //   | k-step 2 of m = 0, 1 | k-step 2 of m = 2, 3
+  // Protocol, the same for every form (MB, 1 and 0 live row blocks run side by side in one workgroup): one barrier
+  // per chunk, NK in all; the wait in front of it covers this wave's DMA of the chunk (vmcnt(0)) and its reads of
+  // the other stage (lgkmcnt(0): k-step 2 has consumed every one of them already); the DMA into the other stage goes
+  // out after that barrier.  Per accumulator element the k-steps still come 0, 1, 2, 3, chunk after chunk, onto C:
+  // the same bits.  sched_barrier(0) between the groups pins the order (hipcc otherwise sinks the reads).
+  // Measured on the metric config (profiles/upd_pipe_ab.txt): +1.8 % evals/s with the DMA behind the barrier,
+  // +0.7 % with the DMA mid-chunk.
+#define GPK_PIPE_FENCE __builtin_amdgcn_sched_barrier(0);
+#ifndef GPK_UPD_PIPE_DMA
+#define GPK_UPD_PIPE_DMA 1  // 1: the DMA right behind the barrier, as asm (below); 0: the builtin, behind k-steps 0, 1 of m = 0, 1
+#endif
+  // The wave's four global_load_lds of a chunk as one asm statement: hipcc's wait insertion does not see them, so the
+  // fragment reads that follow keep their counted lgkmcnt waits, and the DMA can go out as soon as the barrier has
+  // freed its stage (a whole chunk of lead).  Its completion is this loop's own vmcnt(0) in front of the next barrier;
+  // loads hipcc does count only ever wait longer for it.  M0 (the LDS base of each instruction) is saved and restored;
+  // the s_nop 0 is the M0 write -> LDS-DMA wait state; base (SGPR pair) + 32-bit lane offset addressing.
+#define GPK_PIPE_GLDS_ASM(stage, kc)                                                                      \
+  {                                                                                                       \
+    const char* gk_ = reinterpret_cast<const char*>(gsb + (int64_t)(kc) * GBK);                           \
+    const unsigned l0_ = lds_addr(smem + (stage) * STAGE + (wid * PW) * 1024);                            \
+    unsigned keep_;                                                                                       \
+    asm volatile(                                                                                         \
+        "s_mov_b32 %0, m0\n\t"                                                                            \
+        "s_mov_b32 m0, %5\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %9\n\t"                               \
+        "s_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %9\n\t"                               \
+        "s_mov_b32 m0, %7\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %9\n\t"                               \
+        "s_mov_b32 m0, %8\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, %9\n\t"                               \
+        "s_mov_b32 m0, %0"                                                                                \
+        : "=&s"(keep_)                                                                                    \
+        : "v"(gso[0]), "v"(gso[1]), "v"(gso[2]), "v"(gso[3]), "s"(l0_), "s"(l0_ + 1024u), "s"(l0_ + 2048u), \
+          "s"(l0_ + 3072u), "s"(gk_)                                                                      \
+        : "memory");                                                                                      \
   }
+#define GPK_PIPE_NEXT(kc) ((GPK_ABLATE == 3) ? ((kc) + 1) % NK0 : (kc) + 1)
+#define GPK_PIPE_RDA(dst, m, pp)                                                                          \
+  if ((m) < (MLIM_)) dst[m] = *reinterpret_cast<const vec_t*>(sb + aoff + (m) * 16 * ROWB + (pp));
+#define GPK_PIPE_RDB(dst, n, pp) dst[n] = *reinterpret_cast<const vec_t*>(sb + boff + (n) * 16 * ROWB + (pp));
+#define GPK_PIPE_MF(fa_, fb_, e, M0, M1)                                                                  \
+  _Pragma("unroll") for (int n = 0; n < NBK; ++n)                                                         \
+  _Pragma("unroll") for (int m = (M0); m < (M1); ++m)                                                     \
+    if (m < (MLIM_))                                                                                      \
+      acc[m][n] = CFIRST ? Mfma<T>::op_neg(fa_[m][e], fb_[n][e], acc[m][n])                               \
+                         : Mfma<T>::op(fa_[m][e], fb_[n][e], acc[m][n]);
+#define GPK_PIPE_CHUNK(KC, TAIL)                                                                          \
+  {                                                                                                       \
+    const int kc_ = (KC);                                                                                 \
+    const int st = kc_ & 1;                                                                               \
+    const char* sb = smem + st * STAGE;                                                                   \
+    if (GPK_ABLATE != 5) {                                                                                \
+      __builtin_amdgcn_s_waitcnt(0x0070); /* gfx9 encoding: vmcnt(0), expcnt(7), lgkmcnt(0) */            \
+      __syncthreads();                                                                                    \
+    }                                                                                                     \
+    GPK_PIPE_FENCE                                                                                        \
+    GPK_PIPE_RDA(fa0, 0, p0) GPK_PIPE_RDB(fb0, 0, p0) GPK_PIPE_RDB(fb0, 1, p0) GPK_PIPE_RDA(fa0, 1, p0)   \
+    GPK_PIPE_FENCE                                                                                        \
+    if (GPK_UPD_PIPE_DMA == 1 && kc_ + 1 < NK) GPK_PIPE_GLDS_ASM(st ^ 1, GPK_PIPE_NEXT(kc_));             \
+    GPK_PIPE_FENCE                                                                                        \
+    if (TAIL) { GPK_PIPE_MF(fa1, fb1, 1, 2, 4) }                                                          \
+    GPK_PIPE_FENCE                                                                                        \
+    GPK_PIPE_RDA(fa0, 2, p0) GPK_PIPE_RDA(fa0, 3, p0)                                                     \
+    GPK_PIPE_FENCE                                                                                        \
+    if (TAIL) { GPK_PIPE_MF(fa1, fb1, 1, 0, 2) }                                                          \
+    GPK_PIPE_FENCE                                                                                        \
+    GPK_PIPE_RDB(fb1, 0, p1) GPK_PIPE_RDB(fb1, 1, p1) GPK_PIPE_RDA(fa1, 0, p1) GPK_PIPE_RDA(fa1, 1, p1)   \
+    GPK_PIPE_FENCE                                                                                        \
+    GPK_PIPE_MF(fa0, fb0, 0, 0, 2) GPK_PIPE_MF(fa0, fb0, 1, 0, 2)                                         \
+    GPK_PIPE_FENCE                                                                                        \
+    if (GPK_UPD_PIPE_DMA != 1 && kc_ + 1 < NK) GPK_GLDS(st ^ 1, GPK_PIPE_NEXT(kc_));                      \
+    GPK_PIPE_FENCE                                                                                        \
+    GPK_PIPE_MF(fa0, fb0, 0, 2, 4) GPK_PIPE_MF(fa0, fb0, 1, 2, 4)                                         \
+    GPK_PIPE_FENCE                                                                                        \
+    GPK_PIPE_RDA(fa1, 2, p1) GPK_PIPE_RDA(fa1, 3, p1)                                                     \
+    GPK_PIPE_FENCE                                                                                        \
+    GPK_PIPE_MF(fa1, fb1, 0, 0, 2)                                                                        \
+    GPK_PIPE_FENCE                                                                                        \
+    GPK_PIPE_MF(fa1, fb1, 0, 2, 4)                                                                        \
+    GPK_PIPE_FENCE                                                                                        \
+  }
+#define GPK_PIPE_KLOOP(MLIM)                                                                              \
+  {                                                                                                       \
+    constexpr int MLIM_ = (MLIM);                                                                         \
+    vec_t fa0[MB], fb0[NBK], fa1[MB], fb1[NBK];                                                           \
+    GPK_PIPE_CHUNK(0, false)                                                                              \
+    for (int kc = 1; kc < NK; ++kc) GPK_PIPE_CHUNK(kc, true)                                              \
+    GPK_PIPE_MF(fa1, fb1, 1, 0, 4) /* the last chunk's tail */                                            \
+  }
+  if constexpr (PIPE) {
+    if (mact > 1) {
+      GPK_PIPE_KLOOP(MB)
+    } else if (mact == 1) {
+      GPK_PIPE_KLOOP(1)
+    } else {
+      // no live row block: the barriers and this wave's share of the DMA only
+      for (int kc = 0; kc < NK; ++kc) {
+        if (GPK_ABLATE != 5) {
+          __builtin_amdgcn_s_waitcnt(0x0070);
+          __syncthreads();
+        }
+        if (kc + 1 < NK) GPK_GLDS((kc & 1) ^ 1, GPK_PIPE_NEXT(kc));
+      }
+    }
+  } else {
+    if (mact > 1) {
+      GPK_KLOOP(MB)
+    } else if (mact == 1) {
+      GPK_KLOOP(1)
+    } else {
+      GPK_KLOOP(0)
+    }
+  }
+#undef GPK_PIPE_KLOOP
+#undef GPK_PIPE_CHUNK
+#undef GPK_PIPE_MF
+#undef GPK_PIPE_RDB
+#undef GPK_PIPE_RDA
+#undef GPK_PIPE_NEXT
+#undef GPK_PIPE_GLDS_ASM
+#undef GPK_PIPE_FENCE
 #undef GPK_KLOOP
 #undef GPK_MFMA_STEPS
 #undef GPK_GLDS

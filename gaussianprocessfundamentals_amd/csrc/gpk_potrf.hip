@@ -62,8 +62,8 @@ typedef __attribute__((address_space(3))) void lds_void;
 #endif
 
 #ifndef GPK_ABLATE
-#define GPK_ABLATE 0  // timing-only ablations (wrong results): 1 no C read, 2 no epilogue, 3 K loop x2,
-                      // 4 operands from one L2-resident block, 5 no per-chunk barrier
+#define GPK_ABLATE 0  // timing-only ablations of gemm_kernel (wrong results): 2 no epilogue, 3 K loop x2,
+                      // 4 operands from one L2-resident block, 5 no per-chunk barrier (no C read: GPK_ABLATE_C)
 #endif
 
 constexpr int ROWB = 128;  // bytes of one row of a staged K chunk (8 pieces of 16 B)
@@ -157,13 +157,6 @@ __device__ __forceinline__ bool zero_rows(const GemmArgs& a, int b, int64_t r0, 
   return a.mb != nullptr && r0 >= a.n_pad + a.mb[b] && r1 <= a.y_row;
 }
 
-// One 256-thread workgroup computes a TM x TN tile: acc = A_rows(TM x K) * B_rows(TN x K)^T,
-// K = the panel depth.  Waves 2 x 2, each (TM/2) x (TN/2) = MB x NBK blocks of 16 x 16.
-// Staging: global_load_lds (16 B per lane, no VGPR round trip) into two LDS stages; the chunk
-// kc+1 load is issued before chunk kc's fragment reads and MFMAs and retired by the barrier that
-// ends chunk kc.  K is permuted identically for both operands so that one ds_read_b128 yields
-// the operands of EPC consecutive MFMA k-steps: in k-step s, lane group q = lane >> 4 uses
-// logical piece q + 4 (s / EPC), element s % EPC.
 // C value (i, j) of member b's augmented matrix for the fused K build (m = 0 layout): kernel value +
 // noise on the diagonal, identity padding, the y row (gpk_assemble.hip's classes for m = 0).  ls:
 // the ARD length scales (u = x / ls, the reference kernel with l = 1) or NULL.
@@ -190,18 +183,148 @@ __device__ __forceinline__ double kbuild_value(const FastNode& fn, const double*
   return 0.0;
 }
 
-template <typename T, int MODE, int TM, int TN, int WN, int KB = 0>
-__global__ __launch_bounds__(128 * WN, (WN == 4 && MODE == GEMM_UPDATE) ? 4 : 2) void gemm_kernel(GemmArgs a) {
-  constexpr int EPC = 16 / (int)sizeof(T);   // elements per 16-B piece
-  constexpr int GBK = ROWB / (int)sizeof(T); // K depth per stage (16 f64, 32 f32)
-  constexpr int KS = GBK / 4;                // MFMA k-steps per stage
-  constexpr int WM = 2;                      // waves along M (rows); WN along N (columns)
-  constexpr int NW = WM * WN;                // waves per workgroup
-  constexpr int MB = TM / (16 * WM), NBK = TN / (16 * WN);  // 16 x 16 blocks per wave
-  constexpr int STAGE = (TM + TN) * ROWB;    // bytes per stage
-  constexpr int PW = (TM + TN) / (8 * NW);   // glds wave-instructions (8 rows each) per wave
+// ================================================================================ tile core
+// The trailing-update / panel-solve tile, shared by gemm_kernel (one launch per step) and blk_tile (the BLK
+// task of the persistent chain_kernel).  The two paths must write the same bits, so they run the same K loop
+// over the same geometry.  A caller supplies addresses and a callable dma(stage, kc) that issues this wave's
+// DMA of chunk kc into LDS stage `stage`: that is where the paths differ (cache policy, address form).
+//
+// One workgroup of 2 x WN waves computes a TM x TN tile: acc = A_rows(TM x K) * B_rows(TN x K)^T,
+// K = the panel depth; each wave (TM/2) x (TN/WN) = MB x NBK blocks of 16 x 16.
+// Staging: global_load_lds (16 B per lane, no VGPR round trip) into two LDS stages; the chunk
+// kc+1 load is issued during chunk kc's fragment reads and MFMAs and retired by the barrier that
+// ends chunk kc.  K is permuted identically for both operands so that one ds_read_b128 yields
+// the operands of EPC consecutive MFMA k-steps: in k-step s, lane group q = lane >> 4 uses
+// logical piece q + 4 (s / EPC), element s % EPC.
+// A chunk is staged by PW DMA instructions per wave, each 8 rows of 128 B: instruction i of wave wid writes LDS
+// bytes (wid PW + i) 1024 .. of the stage with rows (wid PW + i) 8 .. + 7 of the chunk's TM A rows followed by
+// its TN B rows.
+template <typename T, int TM, int TN, int WN>
+struct TileCore {
+  static constexpr int EPC = 16 / (int)sizeof(T);    // elements per 16-B piece
+  static constexpr int GBK = ROWB / (int)sizeof(T);  // K depth per stage (16 f64, 32 f32)
+  static constexpr int KS = GBK / 4;                 // MFMA k-steps per stage
+  static constexpr int WM = 2;                       // waves along M (rows); WN along N (columns)
+  static constexpr int NW = WM * WN;                 // waves per workgroup
+  static constexpr int MB = TM / (16 * WM), NBK = TN / (16 * WN);  // 16 x 16 blocks per wave
+  static constexpr int STAGE = (TM + TN) * ROWB;     // bytes per stage
+  static constexpr int PW = (TM + TN) / (8 * NW);    // glds wave-instructions (8 rows each) per wave
+  static constexpr int RSTEP = sizeof(T) == 8 ? 4 : 1;  // C/D rows between an accumulator's registers
+  // where the next chunk's DMA goes: behind the first half of the chunk's MFMAs (f64), or at the top of
+  // the chunk (f32, 8 k-steps per chunk: the top measured faster, 116 vs 112 TF)
+  static constexpr bool GMID = sizeof(T) == 8;
   typedef typename Mfma<T>::acc_t acc_t;
   typedef T vec_t __attribute__((ext_vector_type(EPC)));
+  typedef acc_t Acc[MB][NBK];
+
+  // The C tile goes through a buffer descriptor: one 32-bit per-lane offset (VGPR) plus, for block (m, n)
+  // and register r, this wave-uniform byte offset ((m 16 + r RSTEP) ld + n 16) sizeof(T) in an
+  // SGPR (rows of the C/D layout: row(lane, r) = row(lane, 0) + r RSTEP) -- no 64-bit address
+  // per access, which the 64 loads and stores of a tile would otherwise hold in VGPRs.  ldb_s: ld in bytes.
+  static __device__ __forceinline__ int csoff(int ldb_s, int m, int n, int r) {
+    return (m * 16 + r * RSTEP) * ldb_s + n * 16 * (int)sizeof(T);
+  }
+
+  // A thread's place in a stage (byte offsets): its row of A block 0 and of B block 0, and its two 16-B pieces
+  // (k-steps 0 .. KS/2 - 1 and KS/2 .. KS - 1) of a row; wc: its wave's column among the WN
+  struct Frag {
+    int wc, aoff, boff, p0, p1;
+  };
+
+  // One chunk of the K loop on the first MLIM row blocks: one basic block.  SOLVE: the panel solve (acc += a b
+  // against the lower-triangular inverse: K chunk kc feeds output columns >= kc GBK only); otherwise the update,
+  // C first (acc -= a b).  Order inside a chunk: barrier, all
+  // fragment reads, the MFMAs of the first half of the k-steps, THEN (GMID) the next chunk's global_load_lds,
+  // then the second half.  hipcc's wait insertion treats an outstanding LDS DMA as pending LDS traffic and waits
+  // lgkmcnt(0) for any ds_read issued while one is in flight; with the DMA issued after the first half, the
+  // first MFMAs wait only for their own two fragment reads instead of all of them (the second half's lgkmcnt(0)
+  // falls on reads long completed), and the DMA still has half a chunk plus the next barrier to land.
+  // sched_barrier keeps the scheduler from hoisting the DMA back above the first half.
+  // BARRIER = false is a timing instrument of gemm_kernel (wrong results).
+  // (The k-steps [S0, S1) are a macro local to the chunk, not a helper function: a function is optimised on its own
+  // before it is inlined, and the panel-solve kernels then keep fragment reads of skipped columns and need 32 more
+  // VGPRs.)
+#define GPK_TILE_KSTEPS(S0, S1)                                                                               \
+  _Pragma("unroll") for (int s = (S0); s < (S1); ++s)                                                         \
+  _Pragma("unroll") for (int n = 0; n < NBK; ++n) {                                                           \
+    if (SOLVE && kc * GBK > f.wc * (TN / WN) + n * 16 + 15) continue;                                         \
+    _Pragma("unroll") for (int m = 0; m < MLIM; ++m)                                                          \
+      acc[m][n] = SOLVE ? Mfma<T>::op(fa[m][s / EPC][s % EPC], fb[n][s / EPC][s % EPC], acc[m][n])            \
+                        : Mfma<T>::op_neg(fa[m][s / EPC][s % EPC], fb[n][s / EPC][s % EPC], acc[m][n]);       \
+  }
+  template <int MLIM, bool SOLVE, bool BARRIER, typename Dma>
+  static __device__ __forceinline__ void chunk(Acc& acc, const char* smem, int NK, int kc, const Frag f,
+                                               const Dma& dma) {
+    const int aoff = f.aoff, boff = f.boff, p0 = f.p0, p1 = f.p1;
+    {
+      const int st = kc & 1;
+      // one barrier per chunk, at the top: it retires the chunk kc glds (vmcnt(0)) and frees stage
+      // st ^ 1, read during chunk kc - 1.  The vmcnt(0) is explicit: hipcc's wait insertion does not
+      // always see the LDS write of global_load_lds across the loop back edge.
+      if (BARRIER) {
+        __builtin_amdgcn_s_waitcnt(0x0F70);  // gfx9 encoding: vmcnt(0), expcnt(7), lgkmcnt(15)
+        __syncthreads();
+      }
+      if (!GMID && kc + 1 < NK) dma(st ^ 1, kc + 1);
+      if (MLIM > 0) {
+        const char* sb = smem + st * STAGE;
+        vec_t fa[MB][2], fb[NBK][2];
+        // first-half pieces (k-steps 0 .. KS/2-1) of every fragment first, A0 and B0 leading
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          fa[0][h] = *reinterpret_cast<const vec_t*>(sb + aoff + (h ? p1 : p0));
+#pragma unroll
+          for (int n = 0; n < NBK; ++n)
+            fb[n][h] = *reinterpret_cast<const vec_t*>(sb + boff + n * 16 * ROWB + (h ? p1 : p0));
+#pragma unroll
+          for (int m = 1; m < MLIM; ++m)
+            fa[m][h] = *reinterpret_cast<const vec_t*>(sb + aoff + m * 16 * ROWB + (h ? p1 : p0));
+        }
+        GPK_TILE_KSTEPS(0, KS / 2)
+        if (GMID) {
+          __builtin_amdgcn_sched_barrier(0);
+          if (kc + 1 < NK) dma(st ^ 1, kc + 1);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        GPK_TILE_KSTEPS(KS / 2, KS)
+      } else if (GMID && kc + 1 < NK) {
+        dma(st ^ 1, kc + 1);
+      }
+    }
+  }
+#undef GPK_TILE_KSTEPS
+  // The update's depth is a run-time value: its loop stays rolled, one chunk per iteration and no peeled copy of
+  // one.  The panel solve's depth is NB: unrolled, so that the column skip is decided at compile time.
+  template <int MLIM, bool SOLVE, bool BARRIER, typename Dma>
+  static __device__ __forceinline__ void kloop_form(Acc& acc, const char* smem, int NK, const Frag f, const Dma& dma) {
+    if (SOLVE) {
+      for (int kc = 0; kc < NK; ++kc) chunk<MLIM, SOLVE, BARRIER>(acc, smem, NK, kc, f, dma);
+    } else {
+#pragma nounroll
+      for (int kc = 0; kc < NK; ++kc) chunk<MLIM, SOLVE, BARRIER>(acc, smem, NK, kc, f, dma);
+    }
+  }
+  // ... instantiated per MFMA row count (mact = MB, 1, 0 live 16-row blocks of this wave).  On entry chunk 0 is
+  // in flight into (or has landed in) stage 0.
+  template <bool SOLVE, bool BARRIER, typename Dma>
+  static __device__ __forceinline__ void kloop(Acc& acc, const char* smem, int NK, int mact, const Frag f,
+                                               const Dma& dma) {
+    if (mact > 1) {
+      kloop_form<MB, SOLVE, BARRIER>(acc, smem, NK, f, dma);
+    } else if (mact == 1) {
+      kloop_form<1, SOLVE, BARRIER>(acc, smem, NK, f, dma);
+    } else {
+      kloop_form<0, SOLVE, BARRIER>(acc, smem, NK, f, dma);
+    }
+  }
+};
+
+template <typename T, int MODE, int TM, int TN, int WN, int KB = 0>
+__global__ __launch_bounds__(128 * WN, (WN == 4 && MODE == GEMM_UPDATE) ? 4 : 2) void gemm_kernel(GemmArgs a) {
+  typedef TileCore<T, TM, TN, WN> Core;
+  constexpr int EPC = Core::EPC, GBK = Core::GBK, WM = Core::WM, MB = Core::MB, NBK = Core::NBK;
+  constexpr int STAGE = Core::STAGE, PW = Core::PW, RSTEP = Core::RSTEP;
+  typedef typename Core::vec_t vec_t;
   __shared__ __attribute__((aligned(1024))) char smem[2 * STAGE];
 
   const int b = blockIdx.y;
@@ -286,10 +409,11 @@ __global__ __launch_bounds__(128 * WN, (WN == 4 && MODE == GEMM_UPDATE) ? 4 : 2)
   const int wid = wave_uniform(tid >> 6);
   const int wr = wid / WN, wc = wid % WN;
 
-#ifndef GPK_UPD_PIPE
-#define GPK_UPD_PIPE 1  // 0: the plain K loop for the f64 128 x 128 update tile too (see GPK_PIPE_KLOOP)
-#endif
-  constexpr bool PIPE = GPK_UPD_PIPE && sizeof(T) == 8 && MODE == GEMM_UPDATE && TM == 128 && TN == 128 && WN == 4;
+  // The thread's geometry (DMA sources, the C descriptor, the fragment offsets below) stands here and in blk_tile
+  // in the same words, not in TileCore: computed in helper functions it reaches the compiler in another order and
+  // the pipelined kernels, at 128 of 128 VGPRs, no longer come out instruction for instruction as before.
+  // PIPE: the f64 128 x 128 update runs the software-pipelined form of the K loop (below)
+  constexpr bool PIPE = sizeof(T) == 8 && MODE == GEMM_UPDATE && TM == 128 && TN == 128 && WN == 4;
   static_assert(!PIPE || PW == 4, "GPK_PIPE_GLDS_ASM issues four DMA instructions per wave");
   // per-lane source of each of this wave's glds instructions: rows [0, TM) are A, [TM, TM+TN) B
   const T* src[PW];
@@ -309,6 +433,22 @@ __global__ __launch_bounds__(128 * WN, (WN == 4 && MODE == GEMM_UPDATE) ? 4 : 2)
       gso[i] = (uint32_t)(((int64_t)(r - TM) * ldb + swz(r - TM, lane & 7) * EPC) * (int64_t)sizeof(T));
     }
   }
+  // C first (update): the C read overlaps the first chunk's staging instead of following the last MFMA, and the
+  // epilogue is stores only (+3 % update rate at N = 8192; neutral for f32).  Every element then takes its
+  // products one k-step after another onto C whatever the panel grouping, so the persistent launch's tile
+  // tasks (other groupings) write the same bits -- f32 included (its A negated: exact)
+  const int col = lane & 15;
+  // the C tile through a buffer descriptor (TileCore::csoff)
+  T* const C = (MODE == GEMM_UPDATE) ? W + R * a.ld + a.row0 + tj * TN : W + R * a.ld + a.j0;
+  const uint64_t cu = reinterpret_cast<uint64_t>(C);
+  const uint64_t cuu = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(cu >> 32)) << 32) |
+                       (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)cu);
+  const __amdgpu_buffer_rsrc_t crs = __builtin_amdgcn_make_buffer_rsrc(
+      reinterpret_cast<void*>(cuu), 0, (int)(TM * a.ld * (int64_t)sizeof(T)), 0x00020000);
+  const int cvo = (int)(((int64_t)(wr * (TM / WM) + Mfma<T>::row(lane, 0)) * a.ld + wc * (TN / WN) + col) *
+                        (int64_t)sizeof(T));
+  const int ldb_s = wave_uniform((int)(a.ld * (int64_t)sizeof(T)));
+  // this wave's DMA of chunk kc into a stage; GPK_NEXT: ablation 3 runs the K loop twice over the same chunks
 #define GPK_GLDS(stage, kc)                                                                   \
   {                                                                                           \
     const char* gk_ = reinterpret_cast<const char*>(gsb + (int64_t)(kc) * GBK);               \
@@ -319,36 +459,12 @@ __global__ __launch_bounds__(128 * WN, (WN == 4 && MODE == GEMM_UPDATE) ? 4 : 2)
         glds16(PIPE ? reinterpret_cast<const T*>(gk_ + gso[i]) : src[i] + (int64_t)(kc) * GBK, \
                smem + (stage) * STAGE + (wid * PW + i) * 1024);                               \
   }
+#define GPK_NEXT(kc) ((GPK_ABLATE == 3) ? (kc) % NK0 : (kc))
 
 #ifndef GPK_ABLATE_C
-#define GPK_ABLATE_C 0  // timing-only (wrong results): 1 = the C-first update starts from zero instead of C
+#define GPK_ABLATE_C 0  // timing-only (wrong results): 1 = the update starts from zero instead of C
 #endif
-#ifndef GPK_CFIRST
-#define GPK_CFIRST 1  // f64 update: C loaded into the accumulators before the K loop (A negated)
-#endif
-  // C first: the C read overlaps the first chunk's staging instead of following the last MFMA, and the
-  // epilogue is stores only (+3 % update rate at N = 8192; neutral for f32).  Every element then takes its
-  // products one k-step after another onto C whatever the panel grouping, so the persistent launch's tile
-  // tasks (other groupings) write the same bits -- f32 included (its A negated: exact)
-  constexpr bool CFIRST = (MODE == GEMM_UPDATE) && (GPK_CFIRST || KB != 0);
-  const int col = lane & 15;
-  // C tile through a buffer descriptor: one 32-bit per-lane offset (VGPR) plus, for block (m, n)
-  // and register r, the wave-uniform byte offset ((m 16 + r RSTEP) ld + n 16) sizeof(T) in an
-  // SGPR (rows of the C/D layout: row(lane, r) = row(lane, 0) + r RSTEP) -- no 64-bit address
-  // per access, which the 64 loads and stores of the epilogue would otherwise hold in VGPRs
-  T* const C = (MODE == GEMM_UPDATE) ? W + R * a.ld + a.row0 + tj * TN : W + R * a.ld + a.j0;
-  const uint64_t cu = reinterpret_cast<uint64_t>(C);
-  const uint64_t cuu = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(cu >> 32)) << 32) |
-                       (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)cu);
-  const __amdgpu_buffer_rsrc_t crs = __builtin_amdgcn_make_buffer_rsrc(
-      reinterpret_cast<void*>(cuu), 0, (int)(TM * a.ld * (int64_t)sizeof(T)), 0x00020000);
-  const int cvo = (int)(((int64_t)(wr * (TM / WM) + Mfma<T>::row(lane, 0)) * a.ld + wc * (TN / WN) + col) *
-                        (int64_t)sizeof(T));
-  constexpr int RSTEP = sizeof(T) == 8 ? 4 : 1;
-  const int ldb_s = wave_uniform((int)(a.ld * (int64_t)sizeof(T)));
-#define GPK_CSOFF(m, n, r) (((m) * 16 + (r) * RSTEP) * ldb_s + (n) * 16 * (int)sizeof(T))
-
-  acc_t acc[MB][NBK];
+  typename Core::Acc acc;
   // fused K build: the first chunk's DMA goes out before the evaluation (which no longer touches the
   // staging LDS) and lands while the lanes evaluate their entries
   if (KB != 0) GPK_GLDS(0, 0);
@@ -407,120 +523,59 @@ __global__ __launch_bounds__(128 * WN, (WN == 4 && MODE == GEMM_UPDATE) ? 4 : 2)
             acc[m][n][r] = (T)kbuild_value<KB>(fn, ls, Xb, yb, noise, nn, npad, yrow, ci + m * 16 + r * RSTEP,
                                                cj + n * 16);
     }
+  } else if (MODE == GEMM_UPDATE && GPK_ABLATE_C == 0) {
+#pragma unroll
+    for (int m = 0; m < MB; ++m)
+#pragma unroll
+      for (int n = 0; n < NBK; ++n)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[m][n][r] = BufIO<T>::load(crs, cvo, Core::csoff(ldb_s, m, n, r));
   } else {
 #pragma unroll
     for (int m = 0; m < MB; ++m)
 #pragma unroll
-      for (int n = 0; n < NBK; ++n) {
-        if (CFIRST && GPK_ABLATE_C == 0) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) acc[m][n][r] = BufIO<T>::load(crs, cvo, GPK_CSOFF(m, n, r));
-        } else {
-          acc[m][n] = acc_t{0, 0, 0, 0};
-        }
-      }
+      for (int n = 0; n < NBK; ++n) acc[m][n] = typename Core::acc_t{0, 0, 0, 0};
   }
 
   const int q = lane >> 4, lr = lane & 15;
   const int aoff = (wr * (TM / WM) + lr) * ROWB;
   const int boff = (TM + wc * (TN / WN) + lr) * ROWB;
   const int p0 = swz(lr, q) * 16, p1 = swz(lr, q + 4) * 16;
-
   const int NK0 = (MODE == GEMM_TRSM) ? NB / GBK : a.kdepth / GBK;
-  const int NK = (GPK_ABLATE == 3 && MODE == GEMM_UPDATE) ? 2 * NK0 : NK0;
+  const int NK = (GPK_ABLATE == 3 && MODE == GEMM_UPDATE) ? 2 * NK0 : NK0;  // (ablation 3: twice over the same chunks)
   if (KB == 0) GPK_GLDS(0, 0);
-#ifndef GPK_SETPRIO
-#define GPK_SETPRIO 0  // 1: static priority 1 for the second-dispatched half of the waves (MI355X guide)
-#endif
-  if (GPK_SETPRIO && MODE == GEMM_UPDATE && wid >= NW / 2) __builtin_amdgcn_s_setprio(1);
   // 16-row blocks of this wave that hold a nonzero row: rows >= row_end (below the y row) are zero in
   // every panel, so in the tiles of the y row's block most MFMAs would multiply zeros; those tiles
   // take the guarded form of the chunk (wave-uniform, the other tiles are unaffected)
   const int64_t wrow0 = R + wr * (TM / WM);
   const int mact = a.row_end <= 0 ? MB
                  : (int)(a.row_end <= wrow0 ? 0 : ((a.row_end - wrow0 + 15) / 16 < MB ? (a.row_end - wrow0 + 15) / 16 : MB));
-  // The K loop is instantiated per MFMA row count (MB, 1, 0 live 16-row blocks) so that each form is
-  // one basic block per chunk.  Order inside a chunk: barrier, all fragment reads, the MFMAs of the
-  // first half of the k-steps, THEN the next chunk's global_load_lds, then the second half.  hipcc's
-  // wait insertion treats an outstanding LDS DMA as pending LDS traffic and waits lgkmcnt(0) for any
-  // ds_read issued while one is in flight; with the DMA issued after the first half, the first MFMAs
-  // wait only for their own two fragment reads instead of all of them (the second half's lgkmcnt(0)
-  // falls on reads long completed), and the DMA still has half a chunk plus the next barrier to land.
-  // sched_barrier keeps the scheduler from hoisting the DMA back above the first half.
-#ifndef GPK_GLDS_MID
-#define GPK_GLDS_MID 1
-#endif
-#ifndef GPK_GLDS_MID_F32
-#define GPK_GLDS_MID_F32 0  // f32 (8 k-steps per chunk): the DMA at the top measured faster (116 vs 112 TF)
-#endif
-  constexpr bool GMID = sizeof(T) == 8 ? GPK_GLDS_MID : GPK_GLDS_MID_F32;
-#define GPK_MFMA_STEPS(S0, S1, MLIM)                                                                     \
-  _Pragma("unroll") for (int s = (S0); s < (S1); ++s)                                                    \
-  _Pragma("unroll") for (int n = 0; n < NBK; ++n) {                                                      \
-    /* TRSM against the lower-triangular inverse: K chunk kc feeds output columns >= kc GBK only */      \
-    if (MODE == GEMM_TRSM && kc * GBK > wc * (TN / WN) + n * 16 + 15) continue;                          \
-    _Pragma("unroll") for (int m = 0; m < (MLIM); ++m)                                                   \
-      acc[m][n] = CFIRST ? Mfma<T>::op_neg(fa[m][s / EPC][s % EPC], fb[n][s / EPC][s % EPC], acc[m][n])   \
-                         : Mfma<T>::op(fa[m][s / EPC][s % EPC], fb[n][s / EPC][s % EPC], acc[m][n]);     \
-  }
-#define GPK_KLOOP(MLIM)                                                                                  \
-  for (int kc = 0; kc < NK; ++kc) {                                                                      \
-    const int st = kc & 1;                                                                               \
-    /* one barrier per chunk, at the top: it retires the chunk kc glds (vmcnt(0)) and frees stage       \
-       st ^ 1, read during chunk kc - 1.  The vmcnt(0) is explicit: hipcc's wait insertion does not     \
-       always see the LDS write of global_load_lds across the loop back edge. */                       \
-    if (GPK_ABLATE != 5) {                                                                               \
-      __builtin_amdgcn_s_waitcnt(0x0F70); /* gfx9 encoding: vmcnt(0), expcnt(7), lgkmcnt(15) */        \
-      __syncthreads();                                                                                   \
-    }                                                                                                    \
-    if (!GMID && kc + 1 < NK) GPK_GLDS(st ^ 1, (kc + 1) % NK0);                                  \
-    if ((MLIM) > 0) {                                                                                    \
-      const char* sb = smem + st * STAGE;                                                                \
-      vec_t fa[MB][2], fb[NBK][2];                                                                       \
-      /* first-half pieces (k-steps 0 .. KS/2-1) of every fragment first, A0 and B0 leading */          \
-      _Pragma("unroll") for (int h = 0; h < 2; ++h) {                                                    \
-        fa[0][h] = *reinterpret_cast<const vec_t*>(sb + aoff + (h ? p1 : p0));                           \
-        _Pragma("unroll") for (int n = 0; n < NBK; ++n)                                                  \
-          fb[n][h] = *reinterpret_cast<const vec_t*>(sb + boff + n * 16 * ROWB + (h ? p1 : p0));         \
-        _Pragma("unroll") for (int m = 1; m < (MLIM); ++m)                                               \
-          fa[m][h] = *reinterpret_cast<const vec_t*>(sb + aoff + m * 16 * ROWB + (h ? p1 : p0));         \
-      }                                                                                                  \
-      GPK_MFMA_STEPS(0, KS / 2, MLIM)                                                                    \
-      if (GMID) {                                                                                        \
-        __builtin_amdgcn_sched_barrier(0);                                                               \
-        if (kc + 1 < NK) GPK_GLDS(st ^ 1, (kc + 1) % NK0);                                               \
-        __builtin_amdgcn_sched_barrier(0);                                                               \
-      }                                                                                                  \
-      GPK_MFMA_STEPS(KS / 2, KS, MLIM)                                                                   \
-    } else if (GMID && kc + 1 < NK) {                                                                    \
-      GPK_GLDS(st ^ 1, (kc + 1) % NK0);                                                                  \
-    }                                                                                                    \
-  }
-  // Software-pipelined form of the loop for the f64 128 x 128 update tile (8 waves of 64 x 32: fragments a[4], b[2]
-  // per half h of a chunk; k-steps 2h, 2h + 1 use the half's pieces, elements 0 and 1).  The loop is rotated by one
-  // k-step: a wave carries the second-half pieces of chunk kc - 1 across the barrier and issues that chunk's last
-  // k-step (8 MFMAs, the "tail") behind the first fragment reads of chunk kc, so no wave leaves the barrier with an
-  // empty MFMA queue; every read is issued 4 to 16 MFMAs ahead of its first use, into registers whose previous value
-  // has just died, at fixed places (10 live fragment quads = 40 VGPRs at the peak, 24 in the plain loop; no copies):
-  //   barrier | R1 a0[0] b0[0] b0[1] a0[1] | DMA of chunk kc + 1 | tail m = 2, 3 | R2 a0[2] a0[3] | tail m = 0, 1
-  //   | R3 b1[0] b1[1] a1[0] a1[1] | k-steps 0, 1 of m = 0, 1 | k-steps 0, 1 of m = 2, 3 | R4 a1[2] a1[3]
-  //   | k-step 2 of m = 0, 1 | k-step 2 of m = 2, 3
-  // Protocol, the same for every form (MB, 1 and 0 live row blocks run side by side in one workgroup): one barrier
-  // per chunk, NK in all; the wait in front of it covers this wave's DMA of the chunk (vmcnt(0)) and its reads of
-  // the other stage (lgkmcnt(0): k-step 2 has consumed every one of them already); the DMA into the other stage goes
-  // out after that barrier.  Per accumulator element the k-steps still come 0, 1, 2, 3, chunk after chunk, onto C:
-  // the same bits.  sched_barrier(0) between the groups pins the order (hipcc otherwise sinks the reads).
-  // Measured on the metric config (profiles/upd_pipe_ab.txt): +1.8 % evals/s with the DMA behind the barrier,
-  // +0.7 % with the DMA mid-chunk.
-#define GPK_PIPE_FENCE __builtin_amdgcn_sched_barrier(0);
-#ifndef GPK_UPD_PIPE_DMA
-#define GPK_UPD_PIPE_DMA 1  // 1: the DMA right behind the barrier, as asm (below); 0: the builtin, behind k-steps 0, 1 of m = 0, 1
-#endif
-  // The wave's four global_load_lds of a chunk as one asm statement: hipcc's wait insertion does not see them, so the
-  // fragment reads that follow keep their counted lgkmcnt waits, and the DMA can go out as soon as the barrier has
-  // freed its stage (a whole chunk of lead).  Its completion is this loop's own vmcnt(0) in front of the next barrier;
-  // loads hipcc does count only ever wait longer for it.  M0 (the LDS base of each instruction) is saved and restored;
-  // the s_nop 0 is the M0 write -> LDS-DMA wait state; base (SGPR pair) + 32-bit lane offset addressing.
+  constexpr bool BARRIER = GPK_ABLATE != 5;
+  if constexpr (PIPE) {
+    // Software-pipelined form of the loop for the f64 128 x 128 update tile (8 waves of 64 x 32: fragments a[4], b[2]
+    // per half h of a chunk; k-steps 2h, 2h + 1 use the half's pieces, elements 0 and 1).  The loop is rotated by one
+    // k-step: a wave carries the second-half pieces of chunk kc - 1 across the barrier and issues that chunk's last
+    // k-step (8 MFMAs, the "tail") behind the first fragment reads of chunk kc, so no wave leaves the barrier with an
+    // empty MFMA queue; every read is issued 4 to 16 MFMAs ahead of its first use, into registers whose previous value
+    // has just died, at fixed places (10 live fragment quads = 40 VGPRs at the peak, 24 in the plain loop; no copies):
+    //   barrier | R1 a0[0] b0[0] b0[1] a0[1] | DMA of chunk kc + 1 | tail m = 2, 3 | R2 a0[2] a0[3] | tail m = 0, 1
+    //   | R3 b1[0] b1[1] a1[0] a1[1] | k-steps 0, 1 of m = 0, 1 | k-steps 0, 1 of m = 2, 3 | R4 a1[2] a1[3]
+    //   | k-step 2 of m = 0, 1 | k-step 2 of m = 2, 3
+    // Protocol, the same for every form (MB, 1 and 0 live row blocks run side by side in one workgroup): one barrier
+    // per chunk, NK in all; the wait in front of it covers this wave's DMA of the chunk (vmcnt(0)) and its reads of
+    // the other stage (lgkmcnt(0): k-step 2 has consumed every one of them already); the DMA into the other stage goes
+    // out after that barrier.  Per accumulator element the k-steps still come 0, 1, 2, 3, chunk after chunk, onto C:
+    // the same bits.  sched_barrier(0) between the groups pins the order (hipcc otherwise sinks the reads).
+    // Measured on the metric config (profiles/upd_pipe_ab.txt): +1.8 % evals/s with the DMA behind the barrier,
+    // +0.7 % with the DMA mid-chunk (the builtin, behind k-steps 0, 1 of m = 0, 1; since removed).
+    // It stays a family of macros in this function: written as function templates next to TileCore's loop it did not
+    // compile to the same instructions (the fragment arrays became wide vectors carried through the loop).
+    // Its DMA: the wave's four global_load_lds of a chunk as one asm statement.  hipcc's wait insertion
+    // does not see them, so the fragment reads that follow keep their counted lgkmcnt waits, and the DMA can go out as
+    // soon as the barrier has freed its stage (a whole chunk of lead).  Its completion is the loop's own vmcnt(0) in
+    // front of the next barrier; loads hipcc does count only ever wait longer for it.  M0 (the LDS base of each
+    // instruction) is saved and restored; the s_nop 0 is the M0 write -> LDS-DMA wait state; base (SGPR pair) + 32-bit
+    // lane offset addressing.
 #define GPK_PIPE_GLDS_ASM(stage, kc)                                                                      \
   {                                                                                                       \
     const char* gk_ = reinterpret_cast<const char*>(gsb + (int64_t)(kc) * GBK);                           \
@@ -538,29 +593,27 @@ __global__ __launch_bounds__(128 * WN, (WN == 4 && MODE == GEMM_UPDATE) ? 4 : 2)
           "s"(l0_ + 3072u), "s"(gk_)                                                                      \
         : "memory");                                                                                      \
   }
-#define GPK_PIPE_NEXT(kc) ((GPK_ABLATE == 3) ? ((kc) + 1) % NK0 : (kc) + 1)
+#define GPK_PIPE_FENCE __builtin_amdgcn_sched_barrier(0);
 #define GPK_PIPE_RDA(dst, m, pp)                                                                          \
   if ((m) < (MLIM_)) dst[m] = *reinterpret_cast<const vec_t*>(sb + aoff + (m) * 16 * ROWB + (pp));
 #define GPK_PIPE_RDB(dst, n, pp) dst[n] = *reinterpret_cast<const vec_t*>(sb + boff + (n) * 16 * ROWB + (pp));
 #define GPK_PIPE_MF(fa_, fb_, e, M0, M1)                                                                  \
   _Pragma("unroll") for (int n = 0; n < NBK; ++n)                                                         \
   _Pragma("unroll") for (int m = (M0); m < (M1); ++m)                                                     \
-    if (m < (MLIM_))                                                                                      \
-      acc[m][n] = CFIRST ? Mfma<T>::op_neg(fa_[m][e], fb_[n][e], acc[m][n])                               \
-                         : Mfma<T>::op(fa_[m][e], fb_[n][e], acc[m][n]);
+    if (m < (MLIM_)) acc[m][n] = Mfma<T>::op_neg(fa_[m][e], fb_[n][e], acc[m][n]);
 #define GPK_PIPE_CHUNK(KC, TAIL)                                                                          \
   {                                                                                                       \
     const int kc_ = (KC);                                                                                 \
     const int st = kc_ & 1;                                                                               \
     const char* sb = smem + st * STAGE;                                                                   \
-    if (GPK_ABLATE != 5) {                                                                                \
+    if (BARRIER) {                                                                                        \
       __builtin_amdgcn_s_waitcnt(0x0070); /* gfx9 encoding: vmcnt(0), expcnt(7), lgkmcnt(0) */            \
       __syncthreads();                                                                                    \
     }                                                                                                     \
     GPK_PIPE_FENCE                                                                                        \
     GPK_PIPE_RDA(fa0, 0, p0) GPK_PIPE_RDB(fb0, 0, p0) GPK_PIPE_RDB(fb0, 1, p0) GPK_PIPE_RDA(fa0, 1, p0)   \
     GPK_PIPE_FENCE                                                                                        \
-    if (GPK_UPD_PIPE_DMA == 1 && kc_ + 1 < NK) GPK_PIPE_GLDS_ASM(st ^ 1, GPK_PIPE_NEXT(kc_));             \
+    if (kc_ + 1 < NK) GPK_PIPE_GLDS_ASM(st ^ 1, GPK_NEXT(kc_ + 1));                                       \
     GPK_PIPE_FENCE                                                                                        \
     if (TAIL) { GPK_PIPE_MF(fa1, fb1, 1, 2, 4) }                                                          \
     GPK_PIPE_FENCE                                                                                        \
@@ -571,8 +624,6 @@ __global__ __launch_bounds__(128 * WN, (WN == 4 && MODE == GEMM_UPDATE) ? 4 : 2)
     GPK_PIPE_RDB(fb1, 0, p1) GPK_PIPE_RDB(fb1, 1, p1) GPK_PIPE_RDA(fa1, 0, p1) GPK_PIPE_RDA(fa1, 1, p1)   \
     GPK_PIPE_FENCE                                                                                        \
     GPK_PIPE_MF(fa0, fb0, 0, 0, 2) GPK_PIPE_MF(fa0, fb0, 1, 0, 2)                                         \
-    GPK_PIPE_FENCE                                                                                        \
-    if (GPK_UPD_PIPE_DMA != 1 && kc_ + 1 < NK) GPK_GLDS(st ^ 1, GPK_PIPE_NEXT(kc_));                      \
     GPK_PIPE_FENCE                                                                                        \
     GPK_PIPE_MF(fa0, fb0, 0, 2, 4) GPK_PIPE_MF(fa0, fb0, 1, 2, 4)                                         \
     GPK_PIPE_FENCE                                                                                        \
@@ -591,7 +642,6 @@ __global__ __launch_bounds__(128 * WN, (WN == 4 && MODE == GEMM_UPDATE) ? 4 : 2)
     for (int kc = 1; kc < NK; ++kc) GPK_PIPE_CHUNK(kc, true)                                              \
     GPK_PIPE_MF(fa1, fb1, 1, 0, 4) /* the last chunk's tail */                                            \
   }
-  if constexpr (PIPE) {
     if (mact > 1) {
       GPK_PIPE_KLOOP(MB)
     } else if (mact == 1) {
@@ -599,52 +649,35 @@ __global__ __launch_bounds__(128 * WN, (WN == 4 && MODE == GEMM_UPDATE) ? 4 : 2)
     } else {
       // no live row block: the barriers and this wave's share of the DMA only
       for (int kc = 0; kc < NK; ++kc) {
-        if (GPK_ABLATE != 5) {
+        if (BARRIER) {
           __builtin_amdgcn_s_waitcnt(0x0070);
           __syncthreads();
         }
-        if (kc + 1 < NK) GPK_GLDS((kc & 1) ^ 1, GPK_PIPE_NEXT(kc));
+        if (kc + 1 < NK) GPK_GLDS((kc & 1) ^ 1, GPK_NEXT(kc + 1));
       }
     }
-  } else {
-    if (mact > 1) {
-      GPK_KLOOP(MB)
-    } else if (mact == 1) {
-      GPK_KLOOP(1)
-    } else {
-      GPK_KLOOP(0)
-    }
-  }
 #undef GPK_PIPE_KLOOP
 #undef GPK_PIPE_CHUNK
 #undef GPK_PIPE_MF
 #undef GPK_PIPE_RDB
 #undef GPK_PIPE_RDA
-#undef GPK_PIPE_NEXT
-#undef GPK_PIPE_GLDS_ASM
 #undef GPK_PIPE_FENCE
-#undef GPK_KLOOP
-#undef GPK_MFMA_STEPS
+#undef GPK_PIPE_GLDS_ASM
+  } else {
+    const auto dma = [=](int stage, int kc) __attribute__((always_inline)) { GPK_GLDS(stage, GPK_NEXT(kc)); };
+    Core::template kloop<MODE == GEMM_TRSM, BARRIER>(acc, smem, NK, mact, typename Core::Frag{wc, aoff, boff, p0, p1},
+                                                     dma);
+  }
+#undef GPK_NEXT
 #undef GPK_GLDS
 
   if (GPK_ABLATE == 2 && acc[0][0][0] != (T)12345.678) return;
-  if (MODE == GEMM_UPDATE && GPK_ABLATE != 1 && !CFIRST) {
-    // every C value is loaded before the first store: interleaved load/store pairs may alias,
-    // so hipcc would wait for each load in turn (64 dependent HBM round trips per tile)
-#pragma unroll
-    for (int m = 0; m < MB; ++m)
-#pragma unroll
-      for (int n = 0; n < NBK; ++n)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[m][n][r] = BufIO<T>::load(crs, cvo, GPK_CSOFF(m, n, r)) - acc[m][n][r];
-  }
 #pragma unroll
   for (int m = 0; m < MB; ++m)
 #pragma unroll
     for (int n = 0; n < NBK; ++n)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) BufIO<T>::store(crs, cvo, GPK_CSOFF(m, n, r), acc[m][n][r]);
-#undef GPK_CSOFF
+      for (int r = 0; r < 4; ++r) BufIO<T>::store(crs, cvo, Core::csoff(ldb_s, m, n, r), acc[m][n][r]);
 }
 
 // ================================================================================ read-out
@@ -1172,27 +1205,17 @@ __device__ __forceinline__ void slab_gemm32(const float* A, const float* B, int6
   }
 }
 
-// BLK: C(R.., Cc..) -= A(R.., Kc..) B(Cc.., Kc..)^T on a 128 x 128 tile, K = 128 g: gemm_kernel's update
-// (8 waves of 64 x 32, LDS-DMA staging of 128-B row chunks -- 16 f64 / 32 f32 deep -- in two stages, C first,
-// the next chunk's DMA after the first half of the MFMAs) with write-through C stores.  Rows >= row_end are
-// zero.  Every element takes gemm_kernel's k-steps in its order, C first (both dtypes): the launch path's bits.
-#ifndef GPK_CH_GMID_F32
-#define GPK_CH_GMID_F32 0
-#endif
+// BLK: C(R.., Cc..) -= A(R.., Kc..) B(Cc.., Kc..)^T on a 128 x 128 tile, K = 128 g: gemm_kernel's update tile
+// (8 waves of 64 x 32, C first, TileCore's K loop) with the persistent launch's cache policy on the DMA and on
+// the C accesses (write-through stores: other XCDs read them inside the launch).  Rows >= row_end are zero.
+// Every element takes gemm_kernel's k-steps in its order: the launch path's bits (both dtypes).
 template <typename T>
 __device__ __forceinline__ void blk_tile(T* W, int64_t ld, int64_t R, int64_t Cc, int64_t Kc, int g,
                                          int64_t row_end, char* smem) {
-  constexpr int TM = 128, TN = 128, WN = 4, WM = 2, NW = 8, MB = 4, NBK = 2;
-  constexpr int EPC = 16 / (int)sizeof(T), GBK = ROWB / (int)sizeof(T), KS = GBK / 4;
-  constexpr int RSTEP = sizeof(T) == 8 ? 4 : 1;  // C/D rows of one accumulator's registers
-  // the next chunk's DMA after the first half of the MFMAs (f64) or at the top of the chunk (f32, gemm_kernel's
-  // GPK_GLDS_MID_F32: 8 k-steps per chunk)
-  constexpr bool GMID = sizeof(T) == 8 || GPK_CH_GMID_F32 != 0;
-  constexpr int STAGE = (TM + TN) * ROWB;
-  constexpr int PW = (TM + TN) / (8 * NW);
+  typedef TileCore<T, 128, 128, 4> Core;
+  constexpr int TM = 128, TN = 128, WN = 4, WM = Core::WM, MB = Core::MB, NBK = Core::NBK;
+  constexpr int EPC = Core::EPC, GBK = Core::GBK, STAGE = Core::STAGE, PW = Core::PW;
   const int NK = wave_uniform(g * (NB / GBK));  // depth 128 g: the g panels Kc / 128 .. + g - 1
-  typedef T vec_t __attribute__((ext_vector_type(EPC)));
-  typedef typename Mfma<T>::acc_t acc_t;
   const int tid = opaque_tid();
   const int lane = tid & 63;
   const int wid = wave_uniform(tid >> 6);
@@ -1217,68 +1240,26 @@ __device__ __forceinline__ void blk_tile(T* W, int64_t ld, int64_t R, int64_t Cc
   const int cvo = (int)(((int64_t)(wr * (TM / WM) + Mfma<T>::row(lane, 0)) * ld + wc * (TN / WN) + col) *
                         (int64_t)sizeof(T));
   const int ldb_s = wave_uniform((int)(ld * (int64_t)sizeof(T)));
-#define GPK_CH_CSOFF(m, n, r) (((m) * 16 + (r) * RSTEP) * ldb_s + (n) * 16 * (int)sizeof(T))
-  acc_t acc[MB][NBK];
+  typename Core::Acc acc;
 #pragma unroll
   for (int m = 0; m < MB; ++m)
 #pragma unroll
     for (int n = 0; n < NBK; ++n)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) acc[m][n][r] = BufIO<T>::load_ch(crs, cvo, GPK_CH_CSOFF(m, n, r));
+      for (int r = 0; r < 4; ++r) acc[m][n][r] = BufIO<T>::load_ch(crs, cvo, Core::csoff(ldb_s, m, n, r));
   const int q = lane >> 4, lr = lane & 15;
   const int aoff = (wr * (TM / WM) + lr) * ROWB;
   const int boff = (TM + wc * (TN / WN) + lr) * ROWB;
   const int p0 = swz(lr, q) * 16, p1 = swz(lr, q + 4) * 16;
-#define GPK_CH_GLDS(stage, kc)                                                                   \
-  {                                                                                              \
-    _Pragma("unroll") for (int i = 0; i < PW; ++i)                                               \
-        glds16a<kLdAux>(src[i] + (int64_t)(kc) * GBK, smem + (stage) * STAGE + (wid * PW + i) * 1024); \
-  }
-  GPK_CH_GLDS(0, 0);
+  const auto dma = [=](int stage, int kc) __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < PW; ++i)
+      glds16a<kLdAux>(src[i] + (int64_t)kc * GBK, smem + stage * STAGE + (wid * PW + i) * 1024);
+  };
+  dma(0, 0);
   const int64_t wrow0 = R + wr * (TM / WM);
   const int mact = row_end <= wrow0 ? 0 : ((row_end - wrow0 + 15) / 16 < MB ? (int)((row_end - wrow0 + 15) / 16) : MB);
-#define GPK_CH_STEPS(S0, S1, MLIM)                                                                 \
-  _Pragma("unroll") for (int s = (S0); s < (S1); ++s)                                              \
-  _Pragma("unroll") for (int n = 0; n < NBK; ++n)                                                  \
-  _Pragma("unroll") for (int m = 0; m < (MLIM); ++m)                                               \
-    acc[m][n] = Mfma<T>::op_neg(fa[m][s / EPC][s % EPC], fb[n][s / EPC][s % EPC], acc[m][n]);
-#define GPK_CH_KLOOP(MLIM)                                                                         \
-  for (int kc = 0; kc < NK; ++kc) {                                                                \
-    const int st = kc & 1;                                                                         \
-    __builtin_amdgcn_s_waitcnt(0x0F70);                                                            \
-    __syncthreads();                                                                               \
-    if (!GMID && kc + 1 < NK) GPK_CH_GLDS(st ^ 1, kc + 1);                                         \
-    if ((MLIM) > 0) {                                                                              \
-      const char* sb = smem + st * STAGE;                                                          \
-      vec_t fa[MB][2], fb[NBK][2];                                                                 \
-      _Pragma("unroll") for (int h = 0; h < 2; ++h) {                                              \
-        fa[0][h] = *reinterpret_cast<const vec_t*>(sb + aoff + (h ? p1 : p0));                     \
-        _Pragma("unroll") for (int n = 0; n < NBK; ++n)                                            \
-          fb[n][h] = *reinterpret_cast<const vec_t*>(sb + boff + n * 16 * ROWB + (h ? p1 : p0));   \
-        _Pragma("unroll") for (int m = 1; m < (MLIM); ++m)                                         \
-          fa[m][h] = *reinterpret_cast<const vec_t*>(sb + aoff + m * 16 * ROWB + (h ? p1 : p0));   \
-      }                                                                                            \
-      GPK_CH_STEPS(0, KS / 2, MLIM)                                                                \
-      if (GMID) {                                                                                  \
-        __builtin_amdgcn_sched_barrier(0);                                                         \
-        if (kc + 1 < NK) GPK_CH_GLDS(st ^ 1, kc + 1);                                              \
-        __builtin_amdgcn_sched_barrier(0);                                                         \
-      }                                                                                            \
-      GPK_CH_STEPS(KS / 2, KS, MLIM)                                                               \
-    } else if (GMID && kc + 1 < NK) {                                                              \
-      GPK_CH_GLDS(st ^ 1, kc + 1);                                                                 \
-    }                                                                                              \
-  }
-  if (mact > 1) {
-    GPK_CH_KLOOP(MB)
-  } else if (mact == 1) {
-    GPK_CH_KLOOP(1)
-  } else {
-    GPK_CH_KLOOP(0)
-  }
-#undef GPK_CH_KLOOP
-#undef GPK_CH_STEPS
-#undef GPK_CH_GLDS
+  Core::template kloop<false, true>(acc, smem, NK, mact, typename Core::Frag{wc, aoff, boff, p0, p1}, dma);
   // (through a scalar-typed parameter: __builtin_bit_cast of the vector element acc[m][n][r] itself
   // compiled to four stores of element 0)
 #pragma unroll
@@ -1286,8 +1267,7 @@ __device__ __forceinline__ void blk_tile(T* W, int64_t ld, int64_t R, int64_t Cc
 #pragma unroll
     for (int n = 0; n < NBK; ++n)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) BufIO<T>::store_sc1(crs, cvo, GPK_CH_CSOFF(m, n, r), acc[m][n][r]);
-#undef GPK_CH_CSOFF
+      for (int r = 0; r < 4; ++r) BufIO<T>::store_sc1(crs, cvo, Core::csoff(ldb_s, m, n, r), acc[m][n][r]);
 }
 
 #ifndef GPK_CHAIN_NOINLINE

@@ -1,12 +1,16 @@
-"""Software-pipelined K loop of the f64 128 x 128 trailing-update tile (gemm_kernel, GPK_UPD_PIPE) vs the
-64 x 64 update tile, which keeps the plain loop (needs the MI355X).
+"""Software-pipelined K loop of the f64 128 x 128 trailing-update tile (gemm_kernel) vs the 64 x 64 update
+tile, which runs the plain loop of the shared tile core (needs the MI355X).
 
 The rotated loop carries the last k-step of every chunk across the chunk barrier and reorders the fragment
 reads, but per accumulator element the k-steps still come in the same order onto C loaded first, so the whole
 augmented matrix, the read-outs and info must agree BIT FOR BIT with the 64-tile kernel.  Every case runs the
 launch path (chain 0, lookahead 0) twice: upd_t128_min = 1 (the 128-tile kernel on every trailing update) and
-upd_t128_min = 2^30 (the 64-tile kernel on every one).  The two tile sizes agree bitwise with the plain loop
-too (both equal the persistent launch), so this file passes with either form of the loop.
+upd_t128_min = 2^30 (the 64-tile kernel on every one).  Both equal the persistent launch, whose tile task runs
+the plain loop on 128 x 128 tiles.
+
+The same comparison is made between the two panel-solve tile heights (trsm_t128_min = 1 and 2^30, 128 and 64
+rows) and, for an f32 factorisation, between the tile sizes of both kernels: instantiations of the plain loop
+that no other bitwise test singles out.
 
 W is compared on the lower triangle (row >= column) of every member's whole augmented matrix -- L, z, V^T, the
 Schur corner, K^-1 -- which is all the factorisation defines.  Above the diagonal the two tile sizes differ by
@@ -57,12 +61,13 @@ def _lower(f):
     return torch.stack([torch.tril(f.w(b)) for b in range(f.batch)])
 
 
-def _both(fn, **knobs):
-    """fn() -> (factorisation, further results) on the launch path with 128-tile and with 64-tile updates ->
-    two lists of host arrays: W's lower triangles, out, info, then the further results."""
+def _both(fn, vary="upd_t128_min", **knobs):
+    """fn() -> (factorisation, further results) on the launch path with 128-tile and with 64-tile updates (or
+    panel solves: vary = "trsm_t128_min") -> two lists of host arrays: W's lower triangles, out, info, then the
+    further results."""
     out = {}
     for t in (T128, T64):
-        with _Knobs(chain=0, lookahead=0, upd_t128_min=t, **knobs):
+        with _Knobs(chain=0, lookahead=0, **{vary: t}, **knobs):
             f, more = fn()
             torch.cuda.synchronize()
             out[t] = [np.array(r.detach().cpu().numpy(), copy=True) for r in [_lower(f), f.out, f.info] + list(more)]
@@ -73,23 +78,23 @@ def _assert_bitwise(a, b):
     assert len(a) == len(b)
     for u, v in zip(a, b):
         assert u.shape == v.shape and u.dtype == v.dtype
-        assert np.array_equal(u.view(np.uint64) if u.dtype == np.float64 else u,
-                              v.view(np.uint64) if v.dtype == np.float64 else v)
+        bits = {np.dtype(np.float64): np.uint64, np.dtype(np.float32): np.uint32}.get(u.dtype)
+        assert np.array_equal(u.view(bits) if bits else u, v.view(bits) if bits else v)
 
 
-def _plain(n, m, batch, tree=SE, hyps=None, seed=3):
+def _plain(n, m, batch, tree=SE, hyps=None, seed=3, dtype=torch.float64, noise=1e-2):
     x, y = o.make_inputs("C1", n=n, seed=seed)
     dev = engine.device()
     kd = engine.kernel_descriptor(make_kernel(tree, 1), 1)
     hyps = hyps or [[0.1]] * batch
     H = torch.tensor(hyps, dtype=torch.float64, device=dev)
-    NZ = torch.tensor([1e-2], dtype=torch.float64, device=dev)
+    NZ = torch.tensor([noise], dtype=torch.float64, device=dev)
     X = torch.tensor(x, dtype=torch.float64, device=dev).reshape(-1, 1).contiguous()
     Y = torch.tensor(y, dtype=torch.float64, device=dev).reshape(1, -1).contiguous()
     Xs = torch.linspace(-0.1, 1.1, max(m, 1), dtype=torch.float64, device=dev).reshape(-1, 1) if m else None
 
     def run():
-        f = engine.AugmentedFactorization(n, 1, m, batch)
+        f = engine.AugmentedFactorization(n, 1, m, batch, dtype)
         f.W.zero_()
         f.run(kd, H, H.shape[1], NZ, 0, X, 0, Y, 0, Xs, 0)
         return f, ([f.mu, f.var] if m else [])
@@ -105,6 +110,25 @@ def test_row_block_forms_side_by_side(m):
 
 def test_batch_with_test_rows():
     a, b = _both(_plain(777, 64, 3, hyps=[[0.05 + 0.03 * i] for i in range(3)]))
+    _assert_bitwise(a, b)
+
+
+@pytest.mark.parametrize("n,m,batch", [(300, 0, 1), (300, 100, 1), (777, 64, 3)])
+def test_panel_solve_tile_heights(n, m, batch):
+    """128-row vs 64-row panel-solve tiles (update tiles fixed at 128): the y row's block gives the MB / 1 / 0 forms.
+    fuse_trsm = 0: with the look-ahead off, the diagonal-block kernel would otherwise solve the panels of matrices
+    this small itself and gemm_kernel<TRSM> would not be launched at all."""
+    a, b = _both(_plain(n, m, batch, hyps=[[0.05 + 0.03 * i] for i in range(batch)]), vary="trsm_t128_min",
+                 upd_t128_min=T128, fuse_trsm=0)
+    _assert_bitwise(a, b)
+
+
+@pytest.mark.parametrize("vary,fixed", [("upd_t128_min", {}), ("trsm_t128_min", {"upd_t128_min": T128})])
+@pytest.mark.parametrize("n,m", [(300, 0), (300, 100), (1000, 37)])
+def test_f32_tile_sizes(n, m, vary, fixed):
+    """The f32 launch path (the factorisation tests/test_gpu_chain_f32.py compares the persistent launch with):
+    128- vs 64-tile updates, and 128- vs 64-row panel solves."""
+    a, b = _both(_plain(n, m, 1, dtype=torch.float32, noise=1e-1), vary=vary, **fixed)
     _assert_bitwise(a, b)
 
 

@@ -20,8 +20,8 @@ INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 OBJ = os.path.join(HERE, "_obj")
 LIB_NAME = "libgpk.so"
 LIB_PATH = os.path.join(HERE, LIB_NAME)
-SOURCES = ("gpk_assemble.hip", "gpk_diag.hip", "gpk_potrf.hip", "gpk_approx.hip", "gpk_eig.hip", "gpk_flat.hip",
-           "gpk_mean.hip", "gpk_abi.hip")
+SOURCES = ("gpk_assemble.hip", "gpk_grad.hip", "gpk_diag.hip", "gpk_potrf.hip", "gpk_approx.hip", "gpk_eig.hip",
+           "gpk_flat.hip", "gpk_mean.hip", "gpk_abi.hip")
 ARCH = "gfx950"
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-Wno-unused-value"]
 
@@ -91,7 +91,7 @@ def build(force: bool = False, verbose: bool = False, extra=(), out: str = None,
             o = _obj_path(s)
             if force or not os.path.exists(o) or os.path.getmtime(o) < max(hdr_t, os.path.getmtime(os.path.join(CSRC, s))):
                 todo.append(s)
-        # the largest translation units first (gpk_assemble takes ~2 min, the rest ~1 min or less)
+        # the largest translation units first (gpk_assemble, the K build alone, takes ~1.3 min, the rest ~1 min or less)
         todo.sort(key=lambda s: -os.path.getsize(os.path.join(CSRC, s)))
         n = jobs or max(1, min(len(todo), os.cpu_count() or 1, 8))
         if todo:

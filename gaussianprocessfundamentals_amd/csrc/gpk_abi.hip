@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "gpk_internal.h"
+#include "gpk_kernels.h"
 
 using namespace gpk;
 
@@ -92,45 +93,33 @@ bool valid_kdesc(const gpk_kdesc* kd, int64_t d) {
     if (nd.op == GPK_OP_ADD || nd.op == GPK_OP_MUL) {
       if (sp < 2) return false;
       sp -= 1;
-    } else if (nd.op == GPK_OP_LIN) {
+      continue;
+    }
+    // a leaf: its own flag rules, then its hyperparameters (node_params, gpk_kernels.h) inside the vector
+    if (nd.op == GPK_OP_LIN) {
       // one offset per input dimension (+ sg); the node reads the raw points: no ARD slot, no distance form
       if (nd.flags & (GPK_NODE_ARD | GPK_NODE_SE_EXPANDED | GPK_NODE_STANDARD)) return false;
       if (nd.ard_slot != -1) return false;
-      const int need = (int)d + ((nd.flags & GPK_NODE_SCALED) ? 1 : 0);
-      if (nd.hyp_offset < 0 || nd.hyp_offset + need > kd->n_hyp) return false;
-      sp += 1;
-      if (sp > 8) return false;
     } else if (nd.op == GPK_OP_RQ) {
       // [l, a, (sg)]: the direct squared distance of the raw points only -- no ARD slot, no other distance form
       if (nd.flags & (GPK_NODE_ARD | GPK_NODE_SE_EXPANDED | GPK_NODE_STANDARD)) return false;
       if (nd.ard_slot != -1) return false;
-      const int need = 2 + ((nd.flags & GPK_NODE_SCALED) ? 1 : 0);
-      if (nd.hyp_offset < 0 || nd.hyp_offset + need > kd->n_hyp) return false;
-      sp += 1;
-      if (sp > 8) return false;
     } else if (nd.op == GPK_OP_CPW) {
       // change-point window: 1-D inputs, one or two consecutive bounds, one mask form; reads the raw points
       if (kd->dim != 1) return false;
-      const int nb = ((nd.flags & GPK_NODE_CP_LO) ? 1 : 0) + ((nd.flags & GPK_NODE_CP_HI) ? 1 : 0);
-      if (nb == 0) return false;
+      if (cp_bounds(nd.flags) == 0) return false;
       if ((nd.flags & GPK_NODE_CP_SIGMOID) && (nd.flags & GPK_NODE_CP_APPROX)) return false;
       if (nd.flags & (GPK_NODE_SCALED | GPK_NODE_ARD | GPK_NODE_SE_EXPANDED | GPK_NODE_STANDARD)) return false;
       if (nd.ard_slot != -1) return false;
-      if (nd.hyp_offset < 0 || nd.hyp_offset + nb > kd->n_hyp) return false;
-      sp += 1;
-      if (sp > 8) return false;
     } else if (nd.op == GPK_OP_SE || nd.op == GPK_OP_PER || nd.op == GPK_OP_MAT32 ||
                nd.op == GPK_OP_MAT52) {
       const bool ard = (nd.flags & GPK_NODE_ARD) != 0;
       if (ard && (nd.op == GPK_OP_PER || nd.ard_slot < 0 || nd.ard_slot >= kd->n_ard)) return false;
-      int need = (nd.op == GPK_OP_PER) ? 2 : (ard ? (int)d : 1);
-      if (nd.flags & GPK_NODE_SCALED) need += 1;
-      if (nd.hyp_offset < 0 || nd.hyp_offset + need > kd->n_hyp) return false;
-      sp += 1;
-      if (sp > 8) return false;
     } else {
       return false;
     }
+    if (nd.hyp_offset < 0 || nd.hyp_offset + node_params(nd, (int)d) > kd->n_hyp) return false;
+    if (++sp > 8) return false;
   }
   return sp == 1;
 }

@@ -233,7 +233,7 @@ struct GradArgs {
   uint32_t adj_mask[GPK_MAX_NODES];  // per node: nodes whose values multiply its adjoint
 };
 
-// gpk_kernel_vjp (gpk_assemble.hip): adjoints of K(X, Z) = kernel(X, Z) for a weight matrix G [n, ldg]
+// gpk_kernel_vjp (gpk_grad.hip): adjoints of K(X, Z) = kernel(X, Z) for a weight matrix G [n, ldg]
 struct VjpArgs {
   const double* hyp;   // [n_hyp] device
   const double* G;     // dense weights, or (G == NULL) the rank-1 weights gu[i] gv[j]

@@ -1,5 +1,6 @@
-// Device evaluation of the kernel program (shared by the K build in gpk_assemble.hip and the
-// fused first trailing update in gpk_potrf.hip).  Reference formulas: see gpk_assemble.hip.
+// Device evaluation of the kernel program (shared by the K build in gpk_assemble.hip, the gradient
+// kernels in gpk_grad.hip and the fused first trailing update in gpk_potrf.hip).  Reference formulas:
+// see gpk_assemble.hip.
 // Multiply-adds are contracted within a source expression only (fp contract(on)): with hipcc's
 // default (fast) the fusions across statements depend on the inlining context, so the K build's
 // interior / edge loops and the fused build would round a few elements differently.
@@ -51,6 +52,18 @@ __device__ __forceinline__ double cp_ind_dcp(int fl, double x, double cp) {
 
 __host__ __device__ inline int cp_bounds(int fl) {
   return ((fl & GPK_NODE_CP_LO) ? 1 : 0) + ((fl & GPK_NODE_CP_HI) ? 1 : 0);
+}
+
+// Hyperparameters a leaf owns from hyp_offset on: its shape entries -- a window leaf's bounds; the d entries of an
+// ARD node (l_k) or a linear node (c_k); [l, p] of PER and [l, a] of RQ; else the one l -- then sg if it is scaled.
+// The one statement of the rule: valid_kdesc bounds the offsets with it, the gradient kernels write these slots.
+__host__ __device__ inline int node_shape_params(const gpk_node& nd, int d) {
+  if (nd.op == GPK_OP_CPW) return cp_bounds(nd.flags);
+  if ((nd.flags & GPK_NODE_ARD) || nd.op == GPK_OP_LIN) return d;
+  return (nd.op == GPK_OP_PER || nd.op == GPK_OP_RQ) ? 2 : 1;
+}
+__host__ __device__ inline int node_params(const gpk_node& nd, int d) {
+  return node_shape_params(nd, d) + ((nd.flags & GPK_NODE_SCALED) ? 1 : 0);
 }
 
 // w(x) = (1 - ind(x; h[0])) [CP_LO] * ind(x; h[lo ? 1 : 0]) [CP_HI]: the reference's previous-complement times this
@@ -152,11 +165,12 @@ __device__ __forceinline__ double rq_g(double u) {
 }
 
 // number of rational quadratic leaves of a program: one or more selects the instantiations that carry the leaf's
-// code (template parameter RQL of the evaluators below; launch_assemble, launch_grad, launch_vjp).  log1p on top of
-// exp costs registers -- 127 -> 171 VGPRs in the single-node K build, four waves per SIMD down to two -- so the
-// kernels every other program runs compile none of it and are, instruction for instruction, what they were before the
-// leaf existed.  Every evaluation of a program goes through one of those three launches (or the fused first trailing
-// update, single SE / MAT32 / MAT52 nodes only), so an instantiation without the code never sees an RQ node.
+// code (template parameter RQL of the evaluators below; launch_assemble in gpk_assemble.hip, launch_grad and launch_vjp
+// in gpk_grad.hip).  log1p on top of exp costs registers -- 127 -> 171 VGPRs in the single-node K build, four waves
+// per SIMD down to two -- so the kernels every other program runs compile none of it and are, instruction for
+// instruction, what they were before the leaf existed.  Every evaluation of a program goes through one of those three
+// launches (or the fused first trailing update, single SE / MAT32 / MAT52 nodes only), so an instantiation without the
+// code never sees an RQ node.
 __host__ __device__ inline int rq_leaves(const gpk_kdesc& kd) {
   int nr = 0;
   for (int q = 0; q < kd.n_nodes; ++q) nr += kd.nodes[q].op == GPK_OP_RQ ? 1 : 0;

@@ -1,0 +1,237 @@
+"""Hyperparameter fitters (gpbasics/Optimizer/Fitter.py).
+
+``Fitter`` / ``GradientFitter`` keep the reference's constructor (:20-41): the GP receives the data input and the
+metric comes from ``get_metric_by_type``.  The reference's own ``fit`` implementations are a one-step variational SGD
+(:51-170, restated for SKC elsewhere) and a SciPy wrapper that cannot be constructed; neither is provided.
+
+``DeviceLbfgsFitter`` is the fitter this engine was built for: ``n_starts`` restarts of a bound-projected L-BFGS
+advance in lockstep.  Every iteration is ONE batched value + gradient factorisation
+(sweep.native_batched_value_and_gradient -> gpk_nlml_grad) followed by ONE gpk_fit_step launch that runs every
+restart's update, bound projection, line-search decision and convergence test on the device
+(engine.LbfgsState); the host reads the status words back once per ``check_every`` iterations and nothing else.
+"""
+from __future__ import annotations
+
+import math
+from typing import List, Optional, Tuple
+
+import torch
+
+from .. import _native as nat
+from .. import global_parameters as global_param
+from ..DataHandling.DataInput import BatchDataInput, DataInput
+from ..Metrics import Auxiliary as met_aux
+from ..Metrics import MatrixHandlingTypes as mht
+from ..Metrics import Metrics as met
+from . import FitterType as ft
+
+global_param.ensure_init()
+
+
+class Fitter:
+    def __init__(self, data_input, gaussian_process, metric_type: met.MetricType, fitter_type: ft.FitterType,
+                 from_distribution: bool, local_approx: mht.GlobalApproximationsType,
+                 numerical_matrix_handling: mht.NumericalMatrixHandlingType, subset_size: int = None):
+        self._gp = gaussian_process
+        if isinstance(data_input, list):
+            # k-fold: one metric per fold over a copy of the GP (Fitter.py:27-33)
+            self.metric = []
+            for fold in data_input:
+                copied = self._gp.copy()
+                copied.set_data_input(fold)
+                self.metric.append(met_aux.get_metric_by_type(metric_type, copied, local_approx,
+                                                              numerical_matrix_handling, subset_size))
+        else:
+            self._gp.set_data_input(data_input)
+            self.metric = met_aux.get_metric_by_type(metric_type, self._gp, local_approx, numerical_matrix_handling,
+                                                     subset_size)
+        self.data_input = data_input
+        self.type = fitter_type
+        self.from_distribution = bool(from_distribution)
+
+    def fit(self) -> Tuple:
+        """(pre-fit metric, post-fit metric, last hyperparameter list, noise, indices) (Fitter.py:43-44: no body)."""
+        return None
+
+
+class GradientFitter(Fitter):
+    pass
+
+
+def pack_bounds(kernel, xrange, n: int, bounded: bool, optimize_noise: bool):
+    """(lo, hi) float lists of the n_hyp + 1 optimised values, the noise last.  Bounded: the kernel's
+    get_hyper_parameter_bounds (one pair per scalar hyperparameter, a pair of an ARD entry repeated over its values;
+    their +-inf entries kept) and [p_cov_matrix_jitter, inf) for the noise; unbounded: +-inf.  Without
+    ``optimize_noise`` the noise slot is pinned, lo = hi = p_cov_matrix_jitter, whatever ``bounded``."""
+    jitter = float(torch.as_tensor(global_param.p_cov_matrix_jitter))
+    dims = kernel.get_hyper_parameter_dimensionalities()
+    lo: List[float] = []
+    hi: List[float] = []
+    if bounded:
+        bounds = kernel.get_hyper_parameter_bounds(xrange, n)
+        if len(bounds) != len(dims):
+            raise ValueError("the kernel gives %d bounds for %d hyperparameters" % (len(bounds), len(dims)))
+        for (b_lo, b_hi), dim in zip(bounds, dims):
+            k = max(1, int(math.prod(dim)))
+            lo += [float(torch.as_tensor(b_lo))] * k
+            hi += [float(torch.as_tensor(b_hi))] * k
+    else:
+        k = sum(max(1, int(math.prod(dim))) for dim in dims)
+        lo, hi = [-math.inf] * k, [math.inf] * k
+    if optimize_noise:
+        lo.append(jitter if bounded else -math.inf)
+        hi.append(math.inf)
+    else:
+        lo.append(jitter)
+        hi.append(jitter)
+    return lo, hi
+
+
+def split_winner(flat: torch.Tensor, dimensionalities: List[list]) -> List[torch.Tensor]:
+    """The hyperparameter list of a flat DFS-ordered vector: entry i takes prod(dimensionalities[i]) values from the
+    running offset (the reference's deserialize_hyper_parameter slices every entry from 0 for scalars: not used)."""
+    out, off = [], 0
+    for dim in dimensionalities:
+        k = max(1, int(math.prod(dim)))
+        out.append(flat[off:off + k].reshape(list(dim)).clone())
+        off += k
+    if off != flat.numel():
+        raise ValueError("%d values for hyperparameters of %d values" % (flat.numel(), off))
+    return out
+
+
+def _flatten(hyper_parameter: List) -> List[float]:
+    vals: List[float] = []
+    for h in hyper_parameter:
+        vals += [float(v) for v in torch.as_tensor(h, dtype=torch.float64).reshape(-1).tolist()]
+    return vals
+
+
+class DeviceLbfgsFitter(GradientFitter):
+    """Multi-start L-BFGS on the device for the exact, Cholesky-based LL / BIC of a DataInput.
+
+    BIC is 2 LL + a constant for a fixed kernel, so both minimise -LML; pre- and post-fit metrics are the metric's
+    own ``get_metric``.  Start 0 is ``kernel.get_default_hyper_parameter(xrange, n, from_distribution)``, starts 1..
+    are drawn with from_distribution=True under ``generator`` (a CPU torch.Generator; None: torch's global one).
+    ``bounded`` None follows p_check_hyper_parameters.  After ``fit``, ``report`` holds one
+    (f, status name, iterations) per start, ``points`` their accepted points, ``winner`` the index of the returned
+    one, ``steps`` the gpk_fit_step launches and ``status_reads`` the host reads of the status words."""
+
+    def __init__(self, data_input, gaussian_process, metric_type: met.MetricType, fitter_type: ft.FitterType,
+                 from_distribution: bool, local_approx: mht.GlobalApproximationsType,
+                 numerical_matrix_handling: mht.NumericalMatrixHandlingType, subset_size: int = None, *,
+                 n_starts: int = 8, history: int = 8, max_iter: int = 200, gtol: float = 1e-5, ftol: float = 1e-9,
+                 check_every: int = 8, generator: Optional[torch.Generator] = None, bounded: Optional[bool] = None):
+        if isinstance(data_input, list):
+            raise NotImplementedError("DeviceLbfgsFitter: a list of data inputs (k-fold) is not supported")
+        if isinstance(data_input, BatchDataInput):
+            raise NotImplementedError("DeviceLbfgsFitter: BatchDataInput is not supported")
+        if not isinstance(data_input, DataInput):
+            raise NotImplementedError("DeviceLbfgsFitter: data input %s is not supported" % type(data_input).__name__)
+        if metric_type not in (met.MetricType.LL, met.MetricType.BIC):
+            raise NotImplementedError("DeviceLbfgsFitter: metric %s is not supported (LL, BIC)" % metric_type.name)
+        if local_approx is not mht.MatrixApproximations.NONE:
+            raise NotImplementedError("DeviceLbfgsFitter: approximation %s is not supported" % local_approx.name)
+        if numerical_matrix_handling is not mht.NumericalMatrixHandlingType.CHOLESKY_BASED:
+            raise NotImplementedError("DeviceLbfgsFitter: matrix handling %s is not supported (CHOLESKY_BASED)"
+                                      % numerical_matrix_handling.name)
+        from ..MeanFunctionBasics.BaseMeanFunctions import ZeroMeanFunction
+        for owner in (data_input, gaussian_process):
+            mean_function = getattr(owner, "mean_function", None)
+            if mean_function is not None and not isinstance(mean_function, ZeroMeanFunction):
+                raise NotImplementedError("DeviceLbfgsFitter: fitting with the non-zero mean function %s (its "
+                                          "hyperparameters) is not supported" % type(mean_function).__name__)
+        if int(n_starts) < 1 or int(check_every) < 1:
+            raise ValueError("n_starts and check_every must be >= 1")
+        if not 1 <= int(history) <= nat.FIT_MAX_HISTORY:
+            raise ValueError("history must be in [1, %d]" % nat.FIT_MAX_HISTORY)
+        super().__init__(data_input, gaussian_process, metric_type, fitter_type, from_distribution, local_approx,
+                         numerical_matrix_handling, subset_size)
+        self.n_starts, self.history, self.max_iter = int(n_starts), int(history), int(max_iter)
+        self.gtol, self.ftol, self.check_every = float(gtol), float(ftol), int(check_every)
+        self.generator = generator
+        self.bounded = bounded
+        self.report: List[tuple] = []
+        self.steps = 0
+        self.status_reads = 0
+
+    # -- pieces (host only) ---------------------------------------------------------------------
+    def _kernel(self):
+        return self._gp.covariance_matrix.kernel
+
+    def starts(self) -> torch.Tensor:
+        """[n_starts, n_hyp + 1] host tensor: hyperparameters in DFS order, then the noise p_cov_matrix_jitter."""
+        kernel = self._kernel()
+        xrange, n = self.data_input.get_x_range(), self.data_input.n_train
+        jitter = float(torch.as_tensor(global_param.p_cov_matrix_jitter))
+        rows = [_flatten(kernel.get_default_hyper_parameter(xrange, n, self.from_distribution)) + [jitter]]
+        if self.n_starts > 1:
+            if self.generator is not None:
+                # the kernels draw from torch's global generator: run them on the caller's stream of numbers
+                with torch.random.fork_rng(devices=[]):
+                    torch.set_rng_state(self.generator.get_state())
+                    for _ in range(1, self.n_starts):
+                        rows.append(_flatten(kernel.get_default_hyper_parameter(xrange, n, True)) + [jitter])
+                    self.generator.set_state(torch.get_rng_state())
+            else:
+                for _ in range(1, self.n_starts):
+                    rows.append(_flatten(kernel.get_default_hyper_parameter(xrange, n, True)) + [jitter])
+        return torch.tensor(rows, dtype=torch.float64)
+
+    def bounds(self):
+        bounded = bool(global_param.p_check_hyper_parameters) if self.bounded is None else bool(self.bounded)
+        return pack_bounds(self._kernel(), self.data_input.get_x_range(), self.data_input.n_train, bounded,
+                           bool(global_param.p_optimize_noise))
+
+    # -- the fit ------------------------------------------------------------------------------------
+    def fit(self) -> Tuple:
+        from .. import engine, sweep
+        kernel = self._kernel()
+        di = self.data_input
+        dims = kernel.get_hyper_parameter_dimensionalities()
+        x0 = self.starts()
+        lo, hi = self.bounds()
+        n_par = int(x0.shape[1])
+        pre_fit_metric = self.metric.get_metric(split_winner(x0[0, :-1], dims), x0[0, -1].clone())
+
+        evaluate = sweep.native_batched_value_and_gradient(kernel, di.data_x_train, di.get_detrended_y_train())
+        if evaluate.n_par != n_par:
+            raise ValueError("the kernel's device program has %d hyperparameters, its defaults %d"
+                             % (evaluate.n_par - 1, n_par - 1))
+        state = engine.LbfgsState(x0, torch.tensor(lo, dtype=torch.float64), torch.tensor(hi, dtype=torch.float64),
+                                  history=self.history, max_iter=self.max_iter, gtol=self.gtol, ftol=self.ftol)
+        # every restart needs at most max_iter accepted steps, each after at most max_backtracks + 1 trials, twice
+        # (one steepest-descent restart per search) -- the loop ends long before on the status words
+        limit = 2 * self.max_iter * (state.opts.max_backtracks + 2) + 2
+        self.status_reads = 0
+        status = None
+        for k in range(limit):
+            check = (k + 1) % self.check_every == 0
+            # the first evaluation (a timed-out persistent run must not read as BAD_START) and the ones the status
+            # read waits for anyway are verified; in between a timeout is a failed trial, i.e. one more backtrack
+            f, g, info = evaluate(state.x_trial, settle=check or k == 0)
+            state.step(f, g, info)
+            if check:
+                status = state.status.cpu()   # the planned host synchronisation
+                self.status_reads += 1
+                if not bool((status == nat.FIT_RUNNING).any()):
+                    break
+        self.steps = state.steps
+        x, fx, _, iters = state.current()
+        x, fx, iters, status = x.cpu(), fx.cpu(), iters.cpu(), state.status.cpu()
+        self.report = [(float(fx[b]), nat.FIT_STATUS_NAMES[int(status[b])] if 0 <= int(status[b]) < 6 else "INVALID",
+                        int(iters[b])) for b in range(self.n_starts)]
+        ok = torch.isfinite(fx) & (status != nat.FIT_BAD_START) & (status >= 0)
+        if not bool(ok.any()):
+            raise RuntimeError("DeviceLbfgsFitter: no start has a finite objective (%s)" % (self.report,))
+        winner = int(torch.argmin(torch.where(ok, fx, torch.full_like(fx, math.inf))))
+        self.winner = winner
+        self.points = x            # [n_starts, n_hyp + 1]: every start's accepted point (host), the noise last
+        hyper_parameter = split_winner(x[winner, :-1], dims)
+        noise = x[winner, -1].clone()
+        kernel.set_last_hyper_parameter(hyper_parameter)
+        kernel.set_noise(noise)
+        last = kernel.get_last_hyper_parameter()
+        post_fit_metric = self.metric.get_metric(last, kernel.get_noise())
+        # (get_metric records its argument in the kernel, SURVEY Q9: the same list)
+        return pre_fit_metric, post_fit_metric, kernel.get_last_hyper_parameter(), kernel.get_noise(), None

@@ -21,7 +21,7 @@ OBJ = os.path.join(HERE, "_obj")
 LIB_NAME = "libgpk.so"
 LIB_PATH = os.path.join(HERE, LIB_NAME)
 SOURCES = ("gpk_assemble.hip", "gpk_grad.hip", "gpk_diag.hip", "gpk_potrf.hip", "gpk_approx.hip", "gpk_eig.hip",
-           "gpk_flat.hip", "gpk_mean.hip", "gpk_abi.hip")
+           "gpk_flat.hip", "gpk_mean.hip", "gpk_fit.hip", "gpk_abi.hip")
 ARCH = "gfx950"
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-Wno-unused-value"]
 

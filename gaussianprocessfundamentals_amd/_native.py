@@ -41,6 +41,7 @@ EXPORTS = (
     "gpk_kernel_vjp_workspace_bytes", "gpk_kernel_vjp", "gpk_pinv_backward_scale", "gpk_syevd_workspace_bytes",
     "gpk_syevd", "gpk_chain_plan", "gpk_tune_thread", "gpk_chain_stats", "gpk_chain_plan_ex",
     "gpk_op_supported", "gpk_mean_op_supported", "gpk_mean_eval", "gpk_mean_vjp_workspace_bytes", "gpk_mean_vjp",
+    "gpk_fit_state_bytes", "gpk_fit_init", "gpk_fit_step", "gpk_fit_current",
 )
 
 
@@ -64,6 +65,21 @@ class GpkKdesc(ctypes.Structure):
 class GpkMdesc(ctypes.Structure):
     _fields_ = [("n_nodes", c_int32), ("n_hyp", c_int32), ("dim", c_int32), ("reserved", c_int32),
                 ("nodes", GpkNode * MAX_NODES)]
+
+
+class GpkFitOpts(ctypes.Structure):
+    """gpk_fit_opts (include/gpk.h); the defaults are the library's."""
+    _fields_ = [("m", c_int32), ("max_iter", c_int32), ("max_backtracks", c_int32), ("reserved", c_int32),
+                ("c1", c_double), ("gtol", c_double), ("ftol", c_double)]
+
+    def __init__(self, m=8, max_iter=200, max_backtracks=20, c1=1e-4, gtol=1e-5, ftol=1e-9):
+        super().__init__(int(m), int(max_iter), int(max_backtracks), 0, float(c1), float(gtol), float(ftol))
+
+
+# gpk_fit_step status words and the state layout (include/gpk.h)
+FIT_RUNNING, FIT_CONVERGED_G, FIT_CONVERGED_F, FIT_MAX_ITER, FIT_STALLED, FIT_BAD_START = 0, 1, 2, 3, 4, 5
+FIT_STATUS_NAMES = ("RUNNING", "CONVERGED_G", "CONVERGED_F", "MAX_ITER", "STALLED", "BAD_START")
+FIT_HEADER, FIT_MAX_PAR, FIT_MAX_HISTORY = 16, MAX_HYP + 1, 16
 
 
 class GpkLayout(ctypes.Structure):
@@ -147,10 +163,14 @@ def _declare(lib):
         "gpk_mean_vjp_workspace_bytes": (c_size_t, [POINTER(GpkMdesc), c_int64, c_int32]),
         "gpk_mean_vjp": (c_int, [POINTER(GpkMdesc), P, c_int64, P, c_int64, c_int64, c_int32, P, c_int64, P, P,
                                  c_size_t, P]),
+        "gpk_fit_state_bytes": (c_size_t, [c_int, c_int, POINTER(GpkFitOpts)]),
+        "gpk_fit_init": (c_int, [c_int, c_int, POINTER(GpkFitOpts), P, c_int64, P, P, P, P, c_int64, P]),
+        "gpk_fit_step": (c_int, [c_int, c_int, POINTER(GpkFitOpts), P, c_int64, P, c_int64, P, P, P, c_int64, P, P]),
+        "gpk_fit_current": (c_int, [c_int, c_int, P, P, c_int64, P, P, c_int64, P, P]),
     }
     for name, (res, args) in sig.items():
-        if (name == "gpk_op_supported" or name.startswith("gpk_mean_")) and not hasattr(lib, name):
-            continue  # (a library built before the entry existed -- same ABI number: *op_supported() then says no)
+        if (name == "gpk_op_supported" or name.startswith(("gpk_mean_", "gpk_fit_"))) and not hasattr(lib, name):
+            continue  # (a library built before the entry existed: *op_supported() / fit_supported() then say no)
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -192,6 +212,25 @@ def mean_op_supported(op: int) -> bool:
     library built before the mean programs existed."""
     fn = getattr(load_library(), "gpk_mean_op_supported", None)
     return bool(fn is not None and fn(int(op)) == 1)
+
+
+def fit_supported(library=None) -> bool:
+    """Whether the library has the gpk_fit_* entries (added without a new ABI number); False for one built before
+    they existed -- it still loads, and the fitter calls raise NativeUnavailable."""
+    L = library if library is not None else load_library()
+    return all(hasattr(L, n) for n in ("gpk_fit_state_bytes", "gpk_fit_init", "gpk_fit_step", "gpk_fit_current"))
+
+
+def fit_state_bytes(n_par: int, batch: int, opts: "GpkFitOpts" = None) -> int:
+    """gpk_fit_state_bytes (host only): 0 for invalid arguments, with the reason in gpk_last_error."""
+    L = load_library()
+    if not fit_supported(L):
+        raise NativeUnavailable("this libgpk.so was built before the gpk_fit_* entries existed: rebuild it")
+    return int(L.gpk_fit_state_bytes(int(n_par), int(batch), ctypes.byref(opts) if opts is not None else None))
+
+
+def last_error() -> str:
+    return load_library().gpk_last_error().decode()
 
 
 def lib():

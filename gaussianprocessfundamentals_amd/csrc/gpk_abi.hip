@@ -2282,6 +2282,108 @@ int gpk_mean_vjp(const gpk_mdesc* md, const double* hyp_dev, int64_t hyp_stride,
   return 0;
 }
 
+// ---------------------------------------------------------------------------- multi-start L-BFGS step
+static const gpk_fit_opts kFitDefaults = {8, 200, 20, 0, 1e-4, 1e-5, 1e-9};
+
+// the checks every gpk_fit_* entry shares: arguments 1 .. 3; *o receives the options in effect
+static int check_fit_call(int n_par, int batch, const gpk_fit_opts* opts, gpk_fit_opts* o) {
+  *o = opts ? *opts : kFitDefaults;
+  if (n_par < 1 || n_par > GPK_FIT_MAX_PAR) return fail_arg(1, "n_par must be in [1, 65]");
+  if (batch < 1) return fail_arg(2, "batch must be >= 1");
+  if (o->m < 1 || o->m > GPK_FIT_MAX_HISTORY) return fail_arg(3, "opts: m (history) must be in [1, 16]");
+  if (o->max_iter < 1) return fail_arg(3, "opts: max_iter must be >= 1");
+  if (o->max_backtracks < 0) return fail_arg(3, "opts: max_backtracks must be >= 0");
+  if (o->reserved != 0) return fail_arg(3, "opts: the reserved field must be 0");
+  if (!(o->c1 > 0.0 && o->c1 < 1.0)) return fail_arg(3, "opts: c1 must be in (0, 1)");
+  if (!(o->gtol >= 0.0)) return fail_arg(3, "opts: gtol must be >= 0");
+  if (!(o->ftol >= 0.0)) return fail_arg(3, "opts: ftol must be >= 0");
+  return 0;
+}
+
+size_t gpk_fit_state_bytes(int n_par, int batch, const gpk_fit_opts* opts) {
+  gpk_fit_opts o;
+  if (check_fit_call(n_par, batch, opts, &o)) return 0;
+  return (size_t)batch * (size_t)fit_state_doubles(n_par, o.m) * sizeof(double);
+}
+
+int gpk_fit_init(int n_par, int batch, const gpk_fit_opts* opts, const double* x0_dev, int64_t x0_stride,
+                 const double* lo_dev, const double* hi_dev, double* state_dev, double* x_trial_dev,
+                 int64_t xt_stride, void* stream) {
+  gpk_fit_opts o;
+  if (int e = check_fit_call(n_par, batch, opts, &o)) return e;
+  if (!x0_dev) return fail_arg(4, "x0_dev");
+  if (x0_stride < n_par) return fail_arg(5, "x0_stride is smaller than n_par");
+  if (!lo_dev) return fail_arg(6, "lo_dev");
+  if (!hi_dev) return fail_arg(7, "hi_dev");
+  if (!state_dev) return fail_arg(8, "state_dev");
+  if (!x_trial_dev) return fail_arg(9, "x_trial_dev");
+  if (xt_stride < n_par) return fail_arg(10, "xt_stride is smaller than n_par");
+  FitArgs a;
+  memset(&a, 0, sizeof(a));
+  a.n_par = n_par;
+  a.batch = batch;
+  a.m = o.m;
+  a.g = x0_dev;
+  a.g_stride = x0_stride;
+  a.lo = lo_dev;
+  a.hi = hi_dev;
+  a.state = state_dev;
+  a.state_stride = fit_state_doubles(n_par, o.m);
+  a.xt = x_trial_dev;
+  a.xt_stride = xt_stride;
+  GPK_HIP(launch_fit_init(a, reinterpret_cast<hipStream_t>(stream)), "fit_init");
+  return 0;
+}
+
+int gpk_fit_step(int n_par, int batch, const gpk_fit_opts* opts, const double* f_dev, int64_t f_stride,
+                 const double* g_dev, int64_t g_stride, const int32_t* info_dev, double* state_dev,
+                 double* x_trial_dev, int64_t xt_stride, int32_t* status_dev, void* stream) {
+  gpk_fit_opts o;
+  if (int e = check_fit_call(n_par, batch, opts, &o)) return e;
+  if (!f_dev) return fail_arg(4, "f_dev");
+  if (f_stride < 1) return fail_arg(5, "f_stride is smaller than 1");
+  if (!g_dev) return fail_arg(6, "g_dev");
+  if (g_stride < n_par) return fail_arg(7, "g_stride is smaller than n_par");
+  if (!state_dev) return fail_arg(9, "state_dev");
+  if (!x_trial_dev) return fail_arg(10, "x_trial_dev");
+  if (xt_stride < n_par) return fail_arg(11, "xt_stride is smaller than n_par");
+  if (!status_dev) return fail_arg(12, "status_dev");
+  FitArgs a;
+  memset(&a, 0, sizeof(a));
+  a.n_par = n_par;
+  a.batch = batch;
+  a.m = o.m;
+  a.max_iter = o.max_iter;
+  a.max_backtracks = o.max_backtracks;
+  a.c1 = o.c1;
+  a.gtol = o.gtol;
+  a.ftol = o.ftol;
+  a.f = f_dev;
+  a.f_stride = f_stride;
+  a.g = g_dev;
+  a.g_stride = g_stride;
+  a.info = info_dev;
+  a.state = state_dev;
+  a.xt = x_trial_dev;
+  a.xt_stride = xt_stride;
+  a.status = status_dev;
+  GPK_HIP(launch_fit_step(a, reinterpret_cast<hipStream_t>(stream)), "fit_step");
+  return 0;
+}
+
+int gpk_fit_current(int n_par, int batch, const double* state_dev, double* x_dev, int64_t x_stride, double* f_dev,
+                    double* g_dev, int64_t g_stride, int32_t* iters_dev, void* stream) {
+  if (n_par < 1 || n_par > GPK_FIT_MAX_PAR) return fail_arg(1, "n_par must be in [1, 65]");
+  if (batch < 1) return fail_arg(2, "batch must be >= 1");
+  if (!state_dev) return fail_arg(3, "state_dev");
+  if (x_dev && x_stride < n_par) return fail_arg(5, "x_stride is smaller than n_par");
+  if (g_dev && g_stride < n_par) return fail_arg(8, "g_stride is smaller than n_par");
+  GPK_HIP(launch_fit_current(n_par, batch, state_dev, x_dev, x_stride, f_dev, g_dev, g_stride, iters_dev,
+                             reinterpret_cast<hipStream_t>(stream)),
+          "fit_current");
+  return 0;
+}
+
 int gpk_add_diagonal(double* A, int64_t n, int64_t lda, int64_t a_bstride, int32_t batch, double value,
                      void* stream) {
   if (!A && n > 0) return fail_arg(1, "A");

@@ -375,6 +375,30 @@ int64_t mean_blocks(int64_t n);                     // workgroups per member
 hipError_t launch_mean_eval(const gpk_mdesc& md, MeanArgs a, int32_t batch, hipStream_t s);
 hipError_t launch_mean_vjp(const gpk_mdesc& md, MeanArgs a, int32_t batch, double* grad, hipStream_t s);
 
+// multi-start L-BFGS step (gpk_fit.hip); the state layout is the one include/gpk.h documents
+struct FitArgs {
+  int32_t n_par, batch;
+  int32_t m, max_iter, max_backtracks;  // (init: m is written into the state; step reads it back from there)
+  double c1, gtol, ftol;
+  const double* f;     // step: f_t of member b at f[b * f_stride]
+  int64_t f_stride;
+  const double* g;     // step: g_t; init: x0
+  int64_t g_stride;
+  const int32_t* info; // step (may be NULL)
+  const double* lo;    // init
+  const double* hi;    // init
+  double* state;
+  int64_t state_stride;  // init: doubles per member
+  double* xt;
+  int64_t xt_stride;
+  int32_t* status;     // step
+};
+int64_t fit_state_doubles(int n_par, int m);  // per member
+hipError_t launch_fit_init(const FitArgs& a, hipStream_t s);
+hipError_t launch_fit_step(const FitArgs& a, hipStream_t s);
+hipError_t launch_fit_current(int n_par, int batch, const double* state, double* x, int64_t x_stride, double* f,
+                              double* g, int64_t g_stride, int32_t* iters, hipStream_t s);
+
 enum { GEMM_UPDATE = 0, GEMM_TRSM = 1 };
 
 }  // namespace gpk

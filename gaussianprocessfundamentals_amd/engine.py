@@ -1045,3 +1045,104 @@ class DenseFactorization(AugmentedFactorization):
         if not self.inverse:
             raise RuntimeError("DenseFactorization(..., inverse=True) carries the inverse")
         return -self.corner(b)
+
+
+# ------------------------------------------------------------------------ multi-start L-BFGS state
+class LbfgsState:
+    """Device state of ``batch`` L-BFGS restarts advancing in lockstep (gpk_fit_init / gpk_fit_step /
+    gpk_fit_current, include/gpk.h): owns the state buffer, ``x_trial`` [batch, n_par] and ``status`` [batch] int32.
+
+    ``step(f, g, info)`` consumes the evaluation of ``x_trial`` (device tensors, read in place through their strides --
+    e.g. the views sweep.native_batched_value_and_gradient returns) and writes the next ``x_trial``; nothing here
+    synchronises with the host.  ``lo`` / ``hi``: [n_par] bounds shared by the members (None: unbounded)."""
+
+    def __init__(self, x0: torch.Tensor, lo=None, hi=None, history: int = 8, max_iter: int = 200,
+                 max_backtracks: int = 20, c1: float = 1e-4, gtol: float = 1e-5, ftol: float = 1e-9):
+        self.L = nat.lib()
+        if not nat.fit_supported(self.L):
+            raise nat.NativeUnavailable("this libgpk.so was built before the gpk_fit_* entries existed: rebuild it")
+        dev = device()
+        x0 = as_device_f64(x0)
+        if x0.dim() != 2:
+            raise ValueError("x0 must be [batch, n_par]")
+        self.batch, self.n_par = int(x0.shape[0]), int(x0.shape[1])
+        self.opts = nat.GpkFitOpts(history, max_iter, max_backtracks, c1, gtol, ftol)
+        nbytes = nat.fit_state_bytes(self.n_par, self.batch, self.opts)
+        if nbytes == 0:
+            raise ValueError("LbfgsState: %s" % nat.last_error())
+        self.m = int(history)
+        self.stride = nbytes // (8 * self.batch)
+        inf = float("inf")
+        self.lo = (torch.full((self.n_par,), -inf, dtype=torch.float64, device=dev) if lo is None
+                   else as_device_f64(lo).reshape(-1))
+        self.hi = (torch.full((self.n_par,), inf, dtype=torch.float64, device=dev) if hi is None
+                   else as_device_f64(hi).reshape(-1))
+        if self.lo.numel() != self.n_par or self.hi.numel() != self.n_par:
+            raise ValueError("lo and hi must have n_par = %d values" % self.n_par)
+        self.state = torch.empty((self.batch, self.stride), dtype=torch.float64, device=dev)
+        self.x_trial = torch.empty((self.batch, self.n_par), dtype=torch.float64, device=dev)
+        self.status = torch.zeros(self.batch, dtype=torch.int32, device=dev)
+        self.steps = 0
+        nat.check(self.L.gpk_fit_init(self.n_par, self.batch, ctypes.byref(self.opts), nat.ptr(x0), self.n_par,
+                                      nat.ptr(self.lo), nat.ptr(self.hi), nat.ptr(self.state), nat.ptr(self.x_trial),
+                                      self.n_par, nat.stream_handle(dev)), "gpk_fit_init")
+
+    @staticmethod
+    def _strided(name: str, t: torch.Tensor, batch: int, row: Optional[int], dtype) -> int:
+        """The row stride (elements) of a [batch] (row None) or [batch, row] device tensor whose rows are contiguous;
+        the kernel reads batch rows blindly, so the extents are checked here."""
+        if t.dtype != dtype or t.device.type != "cuda":
+            raise ValueError("%s must be a %s device tensor" % (name, dtype))
+        shape = (batch,) if row is None else (batch, row)
+        if tuple(t.shape) != shape:
+            raise ValueError("%s must have shape %s, not %s" % (name, list(shape), list(t.shape)))
+        width = 1 if row is None else row
+        if row is not None and row > 1 and t.stride(1) != 1:
+            raise ValueError("%s: rows must be contiguous" % name)
+        stride = int(t.stride(0)) if batch > 1 else max(int(t.stride(0)), width)
+        if stride < width:
+            raise ValueError("%s: row stride %d is smaller than the row (%d)" % (name, stride, width))
+        return stride
+
+    def step(self, f: torch.Tensor, g: torch.Tensor, info: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One gpk_fit_step launch; returns ``status`` (device int32, not synchronised)."""
+        fs = self._strided("f", f, self.batch, None, torch.float64)
+        gs = self._strided("g", g, self.batch, self.n_par, torch.float64)
+        if info is not None and (info.dtype != torch.int32 or info.numel() != self.batch or not info.is_contiguous()
+                                 or info.device.type != "cuda"):
+            raise ValueError("info must be a contiguous int32 device tensor of %d values" % self.batch)
+        nat.check(self.L.gpk_fit_step(self.n_par, self.batch, ctypes.byref(self.opts), nat.ptr(f), fs, nat.ptr(g), gs,
+                                      nat.ptr(info), nat.ptr(self.state), nat.ptr(self.x_trial), self.n_par,
+                                      nat.ptr(self.status), nat.stream_handle(self.state.device)), "gpk_fit_step")
+        self.steps += 1
+        return self.status
+
+    def current(self):
+        """(x [batch, n_par], f [batch], g [batch, n_par], iterations [batch] int32) of the accepted points."""
+        dev = self.state.device
+        x = torch.empty((self.batch, self.n_par), dtype=torch.float64, device=dev)
+        g = torch.empty_like(x)
+        f = torch.empty(self.batch, dtype=torch.float64, device=dev)
+        it = torch.empty(self.batch, dtype=torch.int32, device=dev)
+        nat.check(self.L.gpk_fit_current(self.n_par, self.batch, nat.ptr(self.state), nat.ptr(x), self.n_par,
+                                         nat.ptr(f), nat.ptr(g), self.n_par, nat.ptr(it), nat.stream_handle(dev)),
+                  "gpk_fit_current")
+        return x, f, g, it
+
+    # -- views of the state (include/gpk.h layout), for inspection --------------------------------
+    def header(self) -> torch.Tensor:
+        return self.state[:, :nat.FIT_HEADER]
+
+    def _block(self, k: int) -> torch.Tensor:
+        o = nat.FIT_HEADER + k * self.n_par
+        return self.state[:, o:o + self.n_par]
+
+    def ring(self):
+        """(S [batch, m, n_par], Y [batch, m, n_par], rho [batch, m], pairs held [batch], next slot [batch])."""
+        o = nat.FIT_HEADER + 5 * self.n_par
+        rho = self.state[:, o:o + self.m]
+        o += self.m
+        S = self.state[:, o:o + self.m * self.n_par].view(self.batch, self.m, self.n_par)
+        o += self.m * self.n_par
+        Y = self.state[:, o:o + self.m * self.n_par].view(self.batch, self.m, self.n_par)
+        return S, Y, rho, self.state[:, 4], self.state[:, 5]

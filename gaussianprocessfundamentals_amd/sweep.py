@@ -106,6 +106,52 @@ def native_batched_evaluator(kernel, X: torch.Tensor, y: torch.Tensor, noise, dt
     return evaluate
 
 
+def native_batched_value_and_gradient(kernel, X: torch.Tensor, y: torch.Tensor, dtype=None):
+    """-LML and its gradient for a batch of (hyperparameters, noise) candidates by ONE identity-augmented batched
+    factorisation per call (gpk_nlml_grad) -- the evaluation a multi-start fitter repeats (Optimizer.Fitter).
+
+    Returns f(cands [B, n_hyp + 1] fp64 on the device, the noise last) -> (f [B], g [B, n_hyp + 1], info [B] int32):
+    device tensors, views of the factorisation's read-out and gradient buffers (valid until the next call with the
+    same B).  One engine.InverseFactorization per batch size is kept and reused; candidate rows are read in place
+    (hyp_stride = noise_stride = n_hyp + 1).
+
+    The call only enqueues: no host synchronisation.  A run that took the persistent launch is NOT settled by a plain
+    call (engine.CHAIN_VERIFY defers that to the first read through the factorisation's accessors, which these views
+    bypass): a wait that timed out shows as info = -1 for its members, which a fitter treats as a failed trial.
+    ``f(cands, settle=True)`` reads through the accessors instead: a persistent run is then verified (one 4-byte
+    read-back, which waits for it) and, had it timed out, run again on the launch path before the views are returned;
+    a run on the launch path has nothing to verify and does not synchronise.  A fitter settles the evaluations it is
+    about to synchronise on anyway, and the first one."""
+    X = engine.as_device_f64(X)
+    yv = engine.as_device_f64(y).reshape(1, -1).contiguous()
+    n, d = int(X.shape[0]), int(X.shape[1])
+    if int(yv.shape[1]) != n:
+        raise ValueError("y has %d values, X has %d points" % (int(yv.shape[1]), n))
+    kd = engine.kernel_descriptor(kernel, d)
+    width = kd.n_hyp + 1
+    dt = dtype or gp.p_dtype
+    cache = {}
+
+    def evaluate(cands: torch.Tensor, settle: bool = False):
+        if cands.dim() != 2 or int(cands.shape[1]) != width:
+            raise ValueError("candidate rows must have %d values (hyperparameters, then the noise)" % width)
+        if cands.dtype != torch.float64 or cands.device != X.device or not cands.is_contiguous():
+            raise ValueError("candidates must be a contiguous float64 tensor on %s" % (X.device,))
+        B = int(cands.shape[0])
+        f = cache.get(B)
+        if f is None:
+            f = cache[B] = engine.InverseFactorization(n, d, B, dt)
+        flat = cands.reshape(-1)
+        # (the noise operand: the same buffer from element n_hyp on; the last member's noise is its last element)
+        f.run(kd, flat, width, flat[kd.n_hyp:], width, X, 0, yv, 0, gradient=True)
+        if settle:
+            return f.nlml(), f.gradient(), f.info
+        return f._out.view(B, 4)[:, 0], f.grad, f._info
+
+    evaluate.n_par = width
+    return evaluate
+
+
 class HyperparameterSweep:
     """Evaluate -LML for every row of a candidate matrix across the ranks of ``group``.
 

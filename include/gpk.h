@@ -457,6 +457,91 @@ int gpk_mean_vjp(const gpk_mdesc* md, const double* hyp_dev, int64_t hyp_stride,
                  int64_t x_bstride, int32_t batch, const double* g, int64_t g_bstride, double* grad_hyp, void* work,
                  size_t work_bytes, void* stream);
 
+/* ------------------------------------------------------------------- multi-start L-BFGS fitter step
+ * The optimiser the batched value + gradient evaluation (gpk_nlml_grad) exists to serve -- the role of the
+ * reference's Optimizer/Fitter.py, as `batch` restarts that advance in lockstep: each iteration is one batched
+ * evaluation of (f, g) at x_trial followed by ONE launch of gpk_fit_step, which runs every member's
+ * bound-projected L-BFGS update, Armijo backtracking decision and convergence test on the device and writes the
+ * next x_trial.  One wave64 per member (four members per 256-thread workgroup, no communication between waves);
+ * lane j owns parameters j and j + 64; every inner product is a fixed-order shuffle tree (no floating-point
+ * atomics: two runs give the same bits, and a member's trajectory does not depend on the batch it runs in).
+ *
+ * Per member, one call consumes (f_t, g_t, info_t) of the current x_trial:
+ *   INIT    accept the trial as (x, f, g); d = -g on the free set; t = min(1, 1 / |d|_2); a failed trial ends the
+ *           member with GPK_FIT_BAD_START.
+ *   SEARCH  the trial fails if info_t != 0, f_t is not finite or any g_t is not finite.  It passes if
+ *           f_t <= f + c1 g^T (x_trial - x) with the actual (projected) displacement and g^T (x_trial - x) <= 0 (so an
+ *           accepted f never increases).  Pass: s = x_trial - x, y = g_t - g, pushed into the ring iff
+ *           s^T y > 2.2e-16 |s| |y| -- otherwise the ring is cleared (the pairs held describe the curvature of another
+ *           region; the next direction is then steepest descent); accept, count one iteration; GPK_FIT_CONVERGED_G if the projected-gradient
+ *           inf-norm <= gtol, else GPK_FIT_CONVERGED_F if f_prev - f <= ftol max(1, |f|, |f_prev|), else
+ *           GPK_FIT_MAX_ITER at max_iter iterations; otherwise a new direction.  Fail: t <- t / 2; after
+ *           max_backtracks halvings the history is cleared and the search restarts from steepest descent -- or, if
+ *           the failing direction was steepest descent already, the member ends with GPK_FIT_STALLED.
+ *   direction  free set F = {j : lo_j < hi_j, not (x_j = lo_j and g_j > 0), not (x_j = hi_j and g_j < 0)}; the
+ *           two-loop recursion on g masked to F with gamma = s^T y / y^T y of the newest pair, masked to F again;
+ *           if d^T g >= 0 the history is cleared and d = -g on F.  t = 1 for a quasi-Newton direction,
+ *           min(1, 1 / |d|_2) for steepest descent.
+ *   trial   x_trial = min(max(fma(t, d, x), lo), hi): the clamp is exact.
+ * A member whose status is not GPK_FIT_RUNNING is frozen: x_trial stays at its accepted x and its state is not
+ * written again.
+ * The four entries were added without a new ABI number (nothing that existed changed meaning): a binding looks the
+ * symbols up and finds them missing in a library built before them.
+ *
+ * State: member b's doubles start at state_dev + b * S, S = gpk_fit_state_bytes / (8 batch) =
+ * GPK_FIT_HEADER + 5 n_par + m + 2 m n_par:
+ *   [GPK_FIT_HEADER] header (integers stored as doubles): 0 phase (0 INIT, 1 SEARCH), 1 status, 2 iterations,
+ *     3 backtracks of the running search, 4 pairs held, 5 ring slot the next pair goes to, 6 f, 7 t, 8 f_prev,
+ *     9 1 if d is steepest descent, 10 evaluations consumed, 11 S, 12 m, 13 n_par, 14 .. 15 zero
+ *   x [n_par], g [n_par], d [n_par], lo [n_par], hi [n_par], rho [m], S [m][n_par], Y [m][n_par]. */
+enum {
+  GPK_FIT_RUNNING = 0,
+  GPK_FIT_CONVERGED_G = 1,
+  GPK_FIT_CONVERGED_F = 2,
+  GPK_FIT_MAX_ITER = 3,
+  GPK_FIT_STALLED = 4,
+  GPK_FIT_BAD_START = 5
+};
+#define GPK_FIT_HEADER 16
+#define GPK_FIT_MAX_PAR (GPK_MAX_HYP + 1)
+#define GPK_FIT_MAX_HISTORY 16
+
+/* NULL where an entry takes one: m 8, max_iter 200, max_backtracks 20, c1 1e-4, gtol 1e-5, ftol 1e-9 */
+typedef struct gpk_fit_opts {
+  int32_t m;              /* pairs kept, 1 .. GPK_FIT_MAX_HISTORY */
+  int32_t max_iter;       /* accepted steps, >= 1 */
+  int32_t max_backtracks; /* halvings of one search, >= 0 */
+  int32_t reserved;       /* 0 */
+  double c1;              /* Armijo constant, in (0, 1) */
+  double gtol;            /* >= 0 */
+  double ftol;            /* >= 0 */
+} gpk_fit_opts;
+
+/* bytes of the state buffer (host only); 0, with a sentence in gpk_last_error, for n_par outside
+ * 1 .. GPK_FIT_MAX_PAR, m outside 1 .. GPK_FIT_MAX_HISTORY, batch < 1 or any other invalid option */
+size_t gpk_fit_state_bytes(int n_par, int batch, const gpk_fit_opts* opts);
+
+/* x0 [batch] rows of n_par (row stride x0_stride >= n_par) clamped into [lo, hi] (device [n_par] each, shared by the
+ * members, +-inf allowed, lo <= hi expected) -> the state's x and x_trial (row stride xt_stride >= n_par). */
+int gpk_fit_init(int n_par, int batch, const gpk_fit_opts* opts, const double* x0_dev, int64_t x0_stride,
+                 const double* lo_dev, const double* hi_dev, double* state_dev, double* x_trial_dev,
+                 int64_t xt_stride, void* stream);
+
+/* One step of every member: f_dev[b * f_stride], g_dev[b * g_stride + j] and info_dev[b] (may be NULL: 0) are the
+ * evaluation at x_trial -- strided so that they may point into a factorisation's read-out ([batch][4], -LML first)
+ * and its gradient buffer without a copy.  status_dev [batch] receives every member's status.  The history length
+ * is the one gpk_fit_init wrote into the state (opts->m is only validated); a state whose n_par is not the call's
+ * gets status -1 and is left alone. */
+int gpk_fit_step(int n_par, int batch, const gpk_fit_opts* opts, const double* f_dev, int64_t f_stride,
+                 const double* g_dev, int64_t g_stride, const int32_t* info_dev, double* state_dev,
+                 double* x_trial_dev, int64_t xt_stride, int32_t* status_dev, void* stream);
+
+/* The accepted point of every member: x_dev (row stride x_stride), f_dev [batch], g_dev (row stride g_stride),
+ * iters_dev [batch]; each may be NULL.  A state whose n_par is not the call's is not read: every output given is
+ * filled with NaN and iters_dev with -1 (the gpk_fit_step status -1 of this call). */
+int gpk_fit_current(int n_par, int batch, const double* state_dev, double* x_dev, int64_t x_stride, double* f_dev,
+                    double* g_dev, int64_t g_stride, int32_t* iters_dev, void* stream);
+
 /* Per-kernel-class timing with HIP events recorded on the launch stream.
  * class: 0 assemble, 1 diag, 2 trsm, 3 update, 4 finalize, 5 trsv, 6 grad */
 #define GPK_NUM_CLASSES 7

@@ -5,18 +5,21 @@
 #include <string.h>
 
 #include <algorithm>
-#include <array>
 #include <atomic>
 #include <initializer_list>
 #include <map>
-#include <queue>
-#include <tuple>
 #include <mutex>
 #include <string>
 #include <vector>
 
+#include "gpk_chain_plan.h"
 #include "gpk_internal.h"
 #include "gpk_kernels.h"
+#include "gpk_tune.h"
+
+#ifndef GPK_DIAG_PROF
+#define GPK_DIAG_PROF 0
+#endif
 
 using namespace gpk;
 
@@ -151,183 +154,6 @@ void adjoint_masks(const gpk_kdesc& kd, uint32_t* mask) {
   }
 }
 
-// Launch-shape thresholds (environment overrides for tuning runs).
-struct Tune {
-  int64_t upd_t128_min;   // 128 x 128 update tiles when at least this many (else 64 x 64)
-  int64_t trsm_t128_min;  // 128-row panel-solve tiles when at least this many (else 64)
-  int64_t diag_dbg;       // timing-only ablation flags of the diagonal kernel (never set in production)
-  int64_t lookahead;      // 1: panel chain on a high-priority side stream, 0: one stream, 2: auto (default:
-                          // on for large matrices, see potrf_impl)
-  int64_t la_min_blocks;  // auto look-ahead: on from this many 128-blocks of the augmented matrix
-  int64_t fuse_trsm;      // f64: panel solve fused into the diagonal-block launch (1: look-ahead off only,
-                          // 2: always; one workgroup per
-  int64_t fuse_trsm_max;  //   64-row tile, each factoring the block) while batch x tiles <= fuse_trsm_max
-  int64_t reserve_cus;    // CUs kept free of the bulk trailing update for the panel chain (32: single N = 8192
-                          // 6.46 -> 6.26 ms, -LML + gradient N = 4096 3.29 -> 3.04 ms, batches of 2 / 8 / 32
-                          // without pipelining +1.9 / +0.6 / +0.4 % against 8)
-  int64_t group;          // panels per trailing update (K = 128 group)
-  int64_t group_first;    // panels of the first group (a short first chain lets the bulk start early)
-  int64_t fuse_kbuild;    // gpk_nlml: K build fused into the first trailing update (single-node kernels)
-  int64_t upd_band;       // trailing-update tile order: 0 row-major, B > 0 bands of B tile rows
-  int64_t skip_zero_rows; // skip the MFMAs of the all-zero 16-row blocks below the y row
-  int64_t syevj_abs_tol_e3; // Jacobi: absolute rotation threshold in units of 1e-3 eps max|a_ii|
-  int64_t diag_version;   // diagonal-block kernel: 2 look-ahead schedule, 1 phase-serial
-  int64_t ingroup;        // in-group updates: 1 left-looking, 2 right-looking, 3 two-level, 0 auto (by batch)
-  int64_t rl_max_tiles;   // auto: right-looking while batch x (block rows) stays below this
-  int64_t band_skip;      // identity extra rows: leave the zero band's tiles out of the grid
-  int64_t group_eye;      // panels per trailing update of identity-augmented factorisations
-  int64_t asm_generic;    // K build: interior tiles through the generic loop too (A/B; bitwise equal)
-  int64_t panel_stream;   // look-ahead panel chain: 0 high-priority side stream, 1 caller's stream,
-                          // 2 normal-priority side stream
-  int64_t trd_split_m;    // gpk_syevd: above this m the tridiagonalisation's A22 v runs over the chip (three
-                          // launches per column) instead of inside one workgroup per panel
-  int64_t chain;          // single f64 factorisations as ONE persistent launch (chain_kernel): 1 auto (default: on
-                          // unless a factorisation enqueued on another stream of the device is still in flight --
-                          // each persistent launch claims every CU, so overlapped factorisations keep the launch
-                          // path: C2 at 4 in flight 1315 vs 779 evals/s), 2 always, 0 off
-  int64_t chain_max_p;    //   ... while the augmented matrix has at most this many rows
-  int64_t chain_grid;     //   workgroups of that launch (0: one per CU)
-  int64_t chain_timeout_ms;  // bound of every wait inside it (then info = -1)
-  int64_t chain_group;    //   panels per deferred tile update (1: every tile update one panel deep; 0: auto,
-                          //   chain_group_for)
-  int64_t chain_max_batch;   // batches of up to this many members run as one persistent launch too ...
-  int64_t chain_batch_max_rows;  // ... while batch x (rows of the augmented matrix) stays within this
-                                 // (batch x span, persistent vs launch path: N = 2048 x 8 1.15 vs 1.38 ms,
-                                 // 4096 x 2 1.87 vs 2.53, 4096 x 4 2.83 vs 3.51; 4096 x 8 5.32 vs 5.07,
-                                 // 2048 x 16 2.02 vs 1.94 -- profiles/r04_chain_batch.jsonl)
-  int64_t chain_uq;       //   the next diagonal block's update split by 32-column quarter (0: one task per slice)
-  int64_t chain_eye;      //   identity-augmented factorisations (the gradient / explicit inverse) too (1: auto as
-                          //   above, 0: never)
-  int64_t chain_max_p_eye;  // ... while their augmented matrix has at most this many rows
-  int64_t asm_feat;       // K build, two-leaf SE + periodic trees on MFMA: per-point features in a pre-pass
-                          // (pair_feat_kernel; 0: staged per tile, A/B -- bitwise equal)
-  int64_t chain_min_p;    // chain = 1 (auto): the launch path below this many rows (a handful of panels: the
-                          // launch path's few launches win -- get_metric N = 128 / 256 / 384 0.119 / 0.165 / 0.216
-                          // vs 0.145 / 0.187 / 0.224 ms, equal at 512, the persistent launch ahead from 768,
-                          // profiles/r05ak_api_small_n_chain_vs_launch.jsonl)
-  int64_t chain_min_p_eye;  // ... and for identity-augmented factorisations (value + gradient): N = 1024 / 1280
-                            // 0.554 / 0.657 ms on the launch path vs 0.590 / 0.683, N = 1536 0.809 vs 0.786
-                            // (profiles/r05al_api_crossover.jsonl)
-  int64_t chain_group_corner;  // identity-augmented plans: panels per deferred update of the corner's tiles (-K^-1,
-                               // read by no later task)
-  int64_t chain_corner_tail;   //   ... except the last this many panels, which keep chain_group
-  int64_t chain_group_la;      // deferred (grouped) tile updates only for block columns at least this many columns
-                               // past the group's last panel
-  int64_t asm_f32_fast;   // f32 K build of a single SE / MAT32 / MAT52 node: the interior tiles through f32_fast_kernel
-                          // (f64 distances, f32 transcendentals; 0: every tile through the general f64 loop, A/B)
-  int64_t chain_group_eye;  // identity-augmented plans: panels per deferred tile update (0: chain_group's rule; 8: value +
-                            // gradient N = 8192 11.33 vs 11.11 ms best, profiles/r06b_grad_sweep_8192.jsonl)
-  int64_t chain_xcd;      // persistent launch: the diagonal chain's tasks as a second list, claimed first by up to
-                          // chain_xcd_seats workgroups of XCD 0 (their hand-offs in one L2); 0: one list
-  int64_t chain_xcd_seats;
-  int64_t asm_f32_chunk;  // f32_fast_kernel: consecutive lower tiles per workgroup (C3: 1 / 2 / 4 / 8 / 16 0.062 / 0.059 /
-                          // 0.059 / 0.063 / 0.073 ms, profiles/r06c_kb_c3_chunks.txt)
-  int64_t chain_f32;      // f32 factorisations as one persistent launch too (chain_kernel<float>: f32 tile tasks, the
-                          // diagonal blocks in f64 as the launch path's); 0: f32 keeps the launch path
-  int64_t chain_group_near;  // tile updates of the columns too near the diagonal for the deferred group: in sub-groups
-                             // of this many panels (same look-ahead rule; 1: panel by panel)
-  int64_t chain_u128;     // the next panel's column below the next diagonal block: one 128 x 128 tile update per block
-                          // row instead of four 32-row slice updates (1; 0: slice updates; 2 auto: slice updates only
-                          // below 48 diagonal blocks on a grid of more than 2 workgroups per diagonal block)
-  int64_t chain_near_la;  // chain_group_near's sub-groups cover the columns at least this many past their last panel
-                          // (1: C2 1866 -> 1884 evals/s, C3 474 -> 480, value + gradient N = 8192 10.6 -> 10.43 ms
-                          // against 2, profiles/r06u_near_la_ab.txt)
-  int64_t chain_s128;     // the panel solves below the next diagonal block: one task per block row (its slices one after
-                          // another) instead of one per 32-row slice (1; 0: per slice; 2 auto: on a grid of at most 2
-                          // workgroups per diagonal block -- the CU-share launches side by side -- and for
-                          // identity-augmented plans of at least 64 diagonal blocks; N = 6144 within the spread either way)
-  int64_t cp_skip;        // K build of a tree with change-point window leaves: a window that is exactly 0.0 for all of a
-                          // tile's row points or all of its column points skips its MUL sibling there (0: never, A/B;
-                          // equal under == for finite sibling values)
-  // (new fields go last: tune() initialises the struct positionally)
-};
-
-int64_t env_i64(const char* name, int64_t dflt) {
-  const char* v = getenv(name);
-  return (v && *v) ? (int64_t)atoll(v) : dflt;
-}
-
-Tune& tune() {
-  static Tune t = {env_i64("GPK_UPD_T128_MIN", 512), env_i64("GPK_TRSM_T128_MIN", 256),
-                         env_i64("GPK_DIAG_DEBUG", 0), env_i64("GPK_LOOKAHEAD", 2), env_i64("GPK_LA_MIN_BLOCKS", 64),
-                         env_i64("GPK_FUSE_TRSM", 1), env_i64("GPK_FUSE_TRSM_MAX", 256),
-                         env_i64("GPK_RESERVE_CUS", 32), env_i64("GPK_GROUP", 8),
-                         env_i64("GPK_GROUP_FIRST", 8), env_i64("GPK_FUSE_KBUILD", 1),
-                         env_i64("GPK_UPD_BAND", 0), env_i64("GPK_SKIP_ZERO_ROWS", 1), env_i64("GPK_SYEVJ_ABS_TOL_E3", 0),
-                         env_i64("GPK_DIAG_VERSION", 2), env_i64("GPK_INGROUP", 0),
-                         env_i64("GPK_RL_MAX_TILES", 256), env_i64("GPK_BAND_SKIP", 1),
-                         env_i64("GPK_GROUP_EYE", 4), env_i64("GPK_ASM_GENERIC", 0),
-                         env_i64("GPK_PANEL_STREAM", 0), env_i64("GPK_TRD_SPLIT_M", 1024),
-                         env_i64("GPK_CHAIN", 1), env_i64("GPK_CHAIN_MAX_P", 12416), env_i64("GPK_CHAIN_GRID", 0),
-                         env_i64("GPK_CHAIN_TIMEOUT_MS", 1000), env_i64("GPK_CHAIN_GROUP", 0),
-                         env_i64("GPK_CHAIN_MAX_BATCH", 8), env_i64("GPK_CHAIN_BATCH_MAX_ROWS", 17500),
-                         env_i64("GPK_CHAIN_UQ", 1), env_i64("GPK_CHAIN_EYE", 1),
-                         env_i64("GPK_CHAIN_MAX_P_EYE", 16640), env_i64("GPK_ASM_FEAT", 1),
-                         env_i64("GPK_CHAIN_MIN_P", 768), env_i64("GPK_CHAIN_MIN_P_EYE", 3072),
-                         env_i64("GPK_CHAIN_GROUP_CORNER", 16), env_i64("GPK_CHAIN_CORNER_TAIL", 8),
-                         env_i64("GPK_CHAIN_GROUP_LA", 2), env_i64("GPK_ASM_F32_FAST", 1),
-                         env_i64("GPK_CHAIN_GROUP_EYE", 8),
-                         env_i64("GPK_CHAIN_XCD", 0), env_i64("GPK_CHAIN_XCD_SEATS", 16),
-                         env_i64("GPK_ASM_F32_CHUNK", 4), env_i64("GPK_CHAIN_F32", 1),
-                         env_i64("GPK_CHAIN_GROUP_NEAR", 2), env_i64("GPK_CHAIN_U128", 2),
-                         env_i64("GPK_CHAIN_NEAR_LA", 1), env_i64("GPK_CHAIN_S128", 2),
-                         env_i64("GPK_CP_SKIP", 1)};
-  return t;
-}
-
-// Knob names of gpk_tune / gpk_tune_thread.
-struct Knob {
-  const char* name;
-  int64_t Tune::*field;
-};
-const Knob kKnobs[] = {
-    {"lookahead", &Tune::lookahead},         {"reserve_cus", &Tune::reserve_cus},
-    {"upd_t128_min", &Tune::upd_t128_min},   {"trsm_t128_min", &Tune::trsm_t128_min},
-    {"diag_debug", &Tune::diag_dbg},         {"group", &Tune::group},
-    {"group_first", &Tune::group_first},     {"fuse_kbuild", &Tune::fuse_kbuild},
-    {"upd_band", &Tune::upd_band},           {"skip_zero_rows", &Tune::skip_zero_rows},
-    {"syevj_abs_tol_e3", &Tune::syevj_abs_tol_e3}, {"diag_version", &Tune::diag_version},
-    {"ingroup", &Tune::ingroup},             {"rl_max_tiles", &Tune::rl_max_tiles},
-    {"band_skip", &Tune::band_skip},         {"group_eye", &Tune::group_eye},
-    {"asm_generic", &Tune::asm_generic},     {"panel_stream", &Tune::panel_stream},
-    {"la_min_blocks", &Tune::la_min_blocks}, {"fuse_trsm", &Tune::fuse_trsm},
-    {"fuse_trsm_max", &Tune::fuse_trsm_max}, {"trd_split_m", &Tune::trd_split_m},
-    {"chain", &Tune::chain},                 {"chain_max_p", &Tune::chain_max_p},
-    {"chain_grid", &Tune::chain_grid},       {"chain_timeout_ms", &Tune::chain_timeout_ms},
-    {"chain_group", &Tune::chain_group},     {"chain_max_batch", &Tune::chain_max_batch},
-    {"chain_batch_max_rows", &Tune::chain_batch_max_rows}, {"chain_uq", &Tune::chain_uq},
-    {"chain_eye", &Tune::chain_eye},         {"chain_max_p_eye", &Tune::chain_max_p_eye},
-    {"asm_feat", &Tune::asm_feat},           {"chain_min_p", &Tune::chain_min_p},
-    {"chain_min_p_eye", &Tune::chain_min_p_eye}, {"chain_group_corner", &Tune::chain_group_corner},
-    {"chain_corner_tail", &Tune::chain_corner_tail}, {"chain_group_la", &Tune::chain_group_la},
-    {"asm_f32_fast", &Tune::asm_f32_fast},
-    {"chain_group_eye", &Tune::chain_group_eye}, {"chain_xcd", &Tune::chain_xcd},
-    {"chain_xcd_seats", &Tune::chain_xcd_seats}, {"asm_f32_chunk", &Tune::asm_f32_chunk},
-    {"chain_f32", &Tune::chain_f32},         {"chain_group_near", &Tune::chain_group_near},
-    {"chain_u128", &Tune::chain_u128},         {"chain_near_la", &Tune::chain_near_la},
-    {"chain_s128", &Tune::chain_s128},       {"cp_skip", &Tune::cp_skip},
-};
-
-int64_t Tune::*knob_field(const char* key) {
-  for (const Knob& k : kKnobs)
-    if (!strcmp(key, k.name)) return k.field;
-  return nullptr;
-}
-
-// Per-host-thread overrides (gpk_tune_thread): a caller that runs its own schedule -- e.g. the
-// pipelined sweep's factorisations on several streams -- pins knobs for its own calls without
-// changing them for other threads.
-thread_local std::vector<std::pair<int64_t Tune::*, int64_t>> t_tune_over;
-
-// The knobs in effect for one call on this thread: one snapshot per call, so a gpk_tune from
-// another thread (ctypes releases the GIL during the enqueue) cannot change a decision midway.
-Tune tune_now() {
-  Tune t = tune();
-  for (const auto& o : t_tune_over) t.*(o.first) = o.second;
-  return t;
-}
-
-
 // Per host thread and device: the high-priority panel stream, the bulk-update stream (created
 // with a CU mask that leaves tune().reserve_cus CUs to the panel chain, so that the
 // diagonal-block kernel -- one workgroup of 150 KB LDS per batch member -- never waits for a CU
@@ -427,41 +253,16 @@ int32_t* fuse_counters(hipStream_t s) {
 
 
 // ------------------------------------------------------------------------ persistent factorisation
-// Task order of chain_kernel (gpk_potrf.hip) for one shape: the task graph (D / S / U32 / BLK, see there)
-// list-scheduled on `grid` workers with estimated durations, highest bottom level (longest path to the
-// end) first; the order in which the simulation starts the tasks is a topological order, which the
-// kernel needs (every task waits only for tasks claimed before it), and puts the diagonal chain ahead
-// of the trailing tiles whenever both are ready.
+// The task list of one shape on the device (its order: chain_order, gpk_chain_plan.h), uploaded at the shape's
+// first call.
 struct ChainPlan {
   int32_t* tasks = nullptr;  // device [ntasks + ntasks_b][4]: list A, then list B (chain_xcd)
   int32_t ntasks = 0, ntasks_b = 0;
   int32_t nblk = 0, nsl = 0, nbc = 0;
 };
 std::mutex g_chain_mu;
-// key: device, n_pad, y_row, grid, members, eye, and every knob chain_order reads (ChainKnobs)
-std::map<std::tuple<int, int64_t, int64_t, int, int, int, int, int, int, int, int, int, int, int, int, int>, ChainPlan>
-    g_chain_plans;
+std::map<ChainPlanKey, ChainPlan> g_chain_plans;
 
-enum { CHT_D = 0, CHT_S = 1, CHT_U32 = 2, CHT_BLK = 3 };
-
-// chain_xcd: the diagonal chain's tasks -- D, the panel solves of the next diagonal block's slices (S / SQ), its
-// quarter updates (UQ) or, without quarters, its per-slice updates (U32 of block column k + 1 on its own rows) --
-// move to list B, in their order; the rest stays list A.  Both lists keep the topological order.  Returns nb.
-int32_t chain_split_lists(std::vector<int32_t>& ord) {
-  std::vector<int32_t> la, lb;
-  la.reserve(ord.size());
-  for (size_t t = 0; t + 3 < ord.size(); t += 4) {
-    const int tyg = ord[t], ty = tyg & 3, g = ((tyg >> 2) & 15) + 1, k = ord[t + 1], r = ord[t + 2], j = ord[t + 3];
-    const bool chain = ty == CHT_D || (ty == CHT_S && (r >> 2) == k + 1) ||
-                       (ty == CHT_U32 && (g > 1 || (j == k + 1 && (r >> 2) == k + 1)));
-    std::vector<int32_t>& dst = chain ? lb : la;
-    dst.insert(dst.end(), ord.begin() + t, ord.begin() + t + 4);
-  }
-  const int32_t nb = (int32_t)(lb.size() / 4);
-  ord.assign(la.begin(), la.end());
-  ord.insert(ord.end(), lb.begin(), lb.end());
-  return nb;
-}
 // Counter scratch of the persistent launch, per (host thread, device, stream): the counters are zeroed
 // by a memset enqueued before each launch, so two threads enqueueing on one stream (torch's null stream
 // is shared by every thread) must never share them -- memset A, memset B, launch A, launch B would hand
@@ -537,333 +338,6 @@ int32_t* g_chain_trace = nullptr;  // GPK_CHAIN_TRACE=1: pinned host words the k
 uint64_t* g_chain_times = nullptr;  // GPK_CHAIN_TIMES=1: device stamps per task of the last profiled launch
 int64_t g_chain_times_n = 0;
 
-
-// panels per deferred tile update: the knob, or (0) 4 below 80 diagonal blocks and 8 from there -- the deep
-// updates' MFMA rate starts to matter more than the columns they hold back (N = 8192 4.46 / 4.49 ms with 4 / 8,
-// 10240 7.74 / 7.62, 12288 12.56 / 12.17, profiles/r04af_chain_group_large.jsonl)
-int chain_group_for(int64_t knob, int64_t n_pad, bool f32 = false) {
-  if (knob > 0) return (int)knob;
-  // (f32: 8 -- C3 at 8 persistent launches in flight 426 / 436 / 427 / 417 evals/s at 4 / 8 / 12 / 16,
-  // profiles/r06j_c3_f32_chain_sweep.txt)
-  return n_pad / NB >= 80 || f32 ? 8 : 4;
-}
-
-// Every tuning input of chain_order, resolved once per call from the knobs (and part of the plan cache key, so a
-// cached device plan and gpk_chain_plan_ex always agree)
-struct ChainKnobs {
-  int group, uq, group_corner, corner_tail, group_la, group_near, u128, near_la, s128;
-};
-ChainKnobs chain_knobs(const Tune& tn, int64_t n_pad, bool eye, bool f32 = false, int grid = 0) {
-  ChainKnobs k;
-  const int64_t gk = eye && tn.chain_group_eye > 0 ? tn.chain_group_eye : tn.chain_group;
-  k.group = std::max(1, std::min(chain_group_for(gk, n_pad, f32), 16));
-  // (f32: one U32 task per slice -- chain_kernel<float> has no quarter-task bodies)
-  k.uq = f32 ? 0 : (int)std::max<int64_t>(0, std::min<int64_t>(2, tn.chain_uq));
-  k.group_corner = (int)std::max<int64_t>(1, std::min<int64_t>(tn.chain_group_corner, 16));
-  k.corner_tail = (int)std::max<int64_t>(0, tn.chain_corner_tail);
-  k.group_la = (int)std::max<int64_t>(1, tn.chain_group_la);
-  k.group_near = (int)std::max<int64_t>(1, std::min<int64_t>(tn.chain_group_near, k.group));
-  k.near_la = (int)std::max<int64_t>(1, tn.chain_near_la);
-  // (auto: slice updates only for short chains on a full grid -- single N = 4096 on 256 workgroups 1.577 vs 1.595 ms;
-  // C2's 64-workgroup launches 1726 -> 1863 evals/s, N = 8192 4.50 -> 4.31 ms, C3 f32 persistent 442 -> 470,
-  // profiles/r06r_chain_u128_ab.txt)
-  k.u128 = tn.chain_u128 == 1 || (tn.chain_u128 == 2 && (n_pad / NB >= 48 || grid <= 2 * (n_pad / NB))) ? 1 : 0;
-  // (auto: the CU-share launches only -- C3 on 8 f32 launches of 64 workgroups 476 -> 495 evals/s, C2 neutral, while a
-  // single N = 8192 on 256 workgroups lost 2 %: 4.27 -> 4.37 ms, profiles/r06x_chain_s128_ab.txt)
-  // and the long identity-augmented plans (value + gradient N = 8192 10.43-10.48 -> 10.32-10.35 ms)
-  k.s128 = tn.chain_s128 == 1 ||
-                   (tn.chain_s128 == 2 && ((grid > 0 && grid <= 2 * (n_pad / NB)) || (eye && n_pad / NB >= 64)))
-               ? 1 : 0;
-  return k;
-}
-
-// list-scheduling durations (us) of D / S / U32 / BLK: the measured per-task run times (round 4, profiles/r04y_*;
-// UQ: half of U32); GPK_CHAIN_DUR="d,s,u,b" overrides them (A/B), read once per process
-const float* chain_durations() {
-  static const std::array<float, 4> dur = [] {
-    std::array<float, 4> d = {28.f, 6.5f, 12.f, 22.5f};
-    if (const char* e = getenv("GPK_CHAIN_DUR")) sscanf(e, "%f,%f,%f,%f", &d[0], &d[1], &d[2], &d[3]);
-    return d;
-  }();
-  return dur.data();
-}
-
-// Type word of a task: ty (bits 0..1) | (g - 1) << 2 (BLK over g panels; UQ: quarter + 1, bits 2..5) |
-// kChainFirst (bit 6: the (slice, block column) cells the task updates have no earlier update -- its counter
-// wait is for 0, not for the task's first panel; identity-augmented lists only) | member << 8.
-constexpr int kChainFirst = 1 << 6;
-// bit 7 on an S task (chain_uq 2): SQ -- the panel solve of a slice of the next diagonal block followed by the
-// slice's lower quarters of that block's update (chain_sq); it publishes sdone after the solve, qdone = 1 at the end
-constexpr int kChainSq = 1 << 7;
-
-// eye: identity extra rows (m = n, gpk_potrf_aug_ex GPK_AUG_EXTRA_IDENTITY).  Extra row t (row n_pad + t) of
-// E L^-T is zero left of column t, so block i >= nblk (extra block e = i - nblk) is zero in every panel q < e
-// (its rows' panel columns are zero until panel e, where its identity entries are solved): the list leaves out
-// every task that would only move zeros -- the panel solves of such slices and the tile updates where either
-// block is still zero -- so the factorisation does n^3 flops (potrf + trtri + lauum) like the launch path's
-// band skip.  The block holding the y row is live in every panel.
-// Returns the task words (four per task); empty if the graph exceeds a bound of the device tasks (the caller
-// reports that as an error -- never reached for graphs built here, whose in-degrees are bounded by construction).
-std::vector<int32_t> chain_order(int64_t n_pad, int64_t y_row, int grid, int nmem, const ChainKnobs& kn,
-                                 bool eye = false) {
-  const int group = kn.group, chain_uq = kn.uq;
-  const int nblk = (int)(n_pad / NB), yb = (int)(y_row / NB), rlast = (int)(y_row / 32);
-  // block i holds a nonzero row in the columns of panel q (monotone in q): from panel live_from(i) on
-  auto live_from = [&](int i) { return (!eye || i < nblk || i == yb) ? 0 : i - nblk; };
-  auto live = [&](int i, int q) { return live_from(i) <= q; };
-  // (flat storage: the lists reach 70 000+ tasks for the identity-augmented N = 8192 -- a vector per task's
-  // dependencies and a map per tile made the first call of a shape cost ~30 ms of host time there)
-  constexpr int MAXDEP = 16;  // D: up to 10 quarter tasks; BLK: 4 + 4 slices + the tile's last update
-  struct Task {
-    int ty, k, r, j;
-    float dur;
-    int nd;
-    int deps[MAXDEP];
-    void dep(int d) {
-      if (nd < MAXDEP) deps[nd] = d;
-      ++nd;
-    }
-  };
-  std::vector<Task> T;
-  T.reserve(4096);
-  const int nr = rlast + 1;
-  std::vector<int> D(nblk, -1), S((size_t)nblk * nr, -1), U((size_t)nblk * nr, -1);
-  const int nbt = yb + 1;
-  std::vector<int> last_upd((size_t)nbt * nbt, -1);  // tile (i, j) -> its latest update task so far
-  auto mk = [](int ty, int k, int r, int j, float du) {
-    Task t;
-    t.ty = ty;
-    t.k = k;
-    t.r = r;
-    t.j = j;
-    t.dur = du;
-    t.nd = 0;
-    return t;
-  };
-  auto s_of = [&](int k, int r) { return S[(size_t)k * nr + r]; };
-  auto u_of = [&](int k, int r) { return U[(size_t)k * nr + r]; };
-  // list-scheduling durations (chain_durations); a tile update over g panels is estimated at b (0.25 + 0.75 g):
-  // the C read / write and the pipeline fill are paid once per task
-  const float* dur = chain_durations();
-  // Deferred tile updates: the panels of group [q0, q1) (G panels) are applied to a tile of block column j
-  // by ONE task of depth 128 (q1 - q0) when j >= q1 + L -- the column is not needed until L steps after
-  // the group's last panel solve; the columns nearer the diagonal take each panel on its own (depth 128),
-  // so the diagonal chain never waits for a deep update.  G = 1 disables it.
-  const int G = group, Gc = kn.group_corner, tail_c = kn.corner_tail, LA = kn.group_la, Gn = kn.group_near;
-  bool overflow = false;  // a task with more than MAXDEP dependencies (unreachable: bounded by construction)
-  auto add = [&](const Task& t) {
-    if (t.nd > MAXDEP) overflow = true;
-    T.push_back(t);
-    return (int)T.size() - 1;
-  };
-  // BLK tasks carry ty = 3 | (g - 1) << 2 for an update over the g panels k .. k + g - 1
-  auto blk = [&](int q0, int g, int i, int jj) {
-    const int ql = q0 + g - 1;  // (S(ql, r) done implies S(q, r) done for every q < ql that has an S task)
-    if (!live(i, ql) || !live(jj, ql)) return;  // (identity rows: zero in every panel of the group)
-    // (identity rows: the group's leading panels in which either block is still zero are left out -- their
-    // products are exact zeros, so the tile's bits are those of the launch path, which includes or skips them)
-    const int f = std::max(live_from(i), live_from(jj));
-    if (f > q0) {
-      g -= f - q0;
-      q0 = f;
-    }
-    Task t = mk(CHT_BLK | ((g - 1) << 2), q0, i, jj, dur[3] * (0.25f + 0.75f * (float)g));
-    for (int s = 4 * i; s <= std::min(4 * i + 3, rlast); ++s) t.dep(s_of(ql, s));
-    if (jj != i)
-      for (int s = 4 * jj; s <= std::min(4 * jj + 3, rlast); ++s) t.dep(s_of(ql, s));
-    int& lu = last_upd[(size_t)i * nbt + jj];
-    if (lu >= 0)
-      t.dep(lu);
-    else if (q0 > 0)
-      t.ty |= kChainFirst;
-    lu = add(t);
-  };
-  // the next diagonal block's update by panel k, split by 32-column quarter (UQ: U32 with the quarter + 1 in
-  // the type word's bits 2..7): 10 tasks of 32 x 32 x 128 on the chain to D(k + 1) instead of 4 of 32 x 128 x
-  // 128, each loading 64 KB of panel instead of 160 (chain_uq; 0: one U32 per slice)
-  const bool uq = chain_uq != 0, sq = chain_uq == 2;
-  std::vector<std::vector<int>> uq_of(nr);  // slice s of diagonal block k + 1 -> its UQ tasks (panel k)
-  for (int k = 0; k < nblk; ++k) {
-    Task d = mk(CHT_D, k, 0, k, dur[0]);
-    if (k > 0)
-      for (int s = 4 * k; s <= std::min(4 * k + 3, rlast); ++s) {
-        if (uq)
-          for (int t : uq_of[s]) d.dep(t);
-        else
-          d.dep(u_of(k - 1, s));
-      }
-    D[k] = add(d);
-    for (int r = 4 * (k + 1); r <= rlast; ++r) {
-      if (!live(r / 4, k)) continue;
-      if (kn.s128 && r >= 4 * (k + 2)) {
-        // chain_s128: below the next diagonal block, a block row's slices take ONE panel-solve task (S with g = the
-        // slice count in the type word's bits 2..5: the slices solved one after another, each as its own S task would)
-        if (r % 4 != 0) continue;
-        const int g = std::min(4, rlast - r + 1);
-        Task t = mk(CHT_S | ((g - 1) << 2), k, r, 0, dur[1] * (0.5f + 0.5f * (float)g));
-        t.dep(D[k]);
-        if (k > 0 && live(r / 4, k - 1)) {
-          for (int s2 = r; s2 < r + g; ++s2) {
-            const int u = u_of(k - 1, s2);
-            bool dup = false;
-            for (int e = 0; e < t.nd && e < MAXDEP; ++e) dup = dup || t.deps[e] == u;
-            if (!dup) t.dep(u);
-          }
-        } else if (k > 0) {
-          t.ty |= kChainFirst;
-        }
-        const int id = add(t);
-        for (int s2 = r; s2 < r + g; ++s2) S[(size_t)k * nr + s2] = id;
-        continue;
-      }
-      // chain_uq 2: the next diagonal block's slices take SQ tasks -- the panel solve followed by the slice's lower
-      // quarters of that block (chain_sq), which need the siblings' solved rows (claimed before: lower slices first)
-      const bool sqt = sq && k + 1 < nblk && r < 4 * (k + 2);
-      Task t = mk(CHT_S | (sqt ? kChainSq : 0), k, r, 0, dur[1] + (sqt ? dur[2] * 0.5f : 0.f));
-      t.dep(D[k]);
-      if (k > 0 && live(r / 4, k - 1))
-        t.dep(u_of(k - 1, r));
-      else if (k > 0)
-        t.ty |= kChainFirst;  // (the slice's first live panel: nothing updated it before)
-      if (sqt) {
-        const int lu = last_upd[(size_t)(k + 1) * nbt + (k + 1)];
-        if (lu >= 0) t.dep(lu);
-        for (int q = 4 * (k + 1); q < r; ++q) t.dep(s_of(k, q));
-      }
-      S[(size_t)k * nr + r] = add(t);
-      if (sqt) {
-        uq_of[r].push_back(S[(size_t)k * nr + r]);
-        U[(size_t)k * nr + r] = S[(size_t)k * nr + r];
-      }
-    }
-    for (int r = 4 * (k + 1); r <= rlast; ++r) {
-      if (!live(r / 4, k)) continue;
-      if (sq && k + 1 < nblk && r < 4 * (k + 2)) continue;  // (done by the slice's SQ task)
-      const int lu = last_upd[(size_t)(r / 4) * nbt + (k + 1)];
-      const int first = (lu < 0 && k > 0) ? kChainFirst : 0;
-      if (uq && k + 1 < nblk && r < 4 * (k + 2)) {
-        const int rl = r - 4 * (k + 1);
-        for (int q = 0; q <= rl; ++q) {  // lower quarters of the diagonal block's slice r
-          Task t = mk(CHT_U32 | ((q + 1) << 2) | first, k, r, k + 1, dur[2] * 0.5f);
-          t.dep(s_of(k, r));
-          if (q != rl) t.dep(s_of(k, 4 * (k + 1) + q));
-          if (lu >= 0) t.dep(lu);
-          uq_of[r].push_back(add(t));
-        }
-        U[(size_t)k * nr + r] = uq_of[r].back();  // (not read: D(k + 1) waits for every quarter)
-        continue;
-      }
-      if (kn.u128 && r >= 4 * (k + 2)) {
-        // chain_u128: below the next diagonal block, the four slices of a block row take ONE 128 x 128 tile update
-        // over panel k (a BLK task: the same k-steps, half the CU time of four slice updates); it publishes every
-        // slice's counter, so each slice's next panel solve waits for the block row instead of its own slice
-        if (r % 4 == 0 || r == 4 * (k + 2)) {
-          blk(k, 1, r / 4, k + 1);
-          const int bt = last_upd[(size_t)(r / 4) * nbt + (k + 1)];
-          for (int s2 = r; s2 <= std::min(4 * (r / 4) + 3, rlast); ++s2) U[(size_t)k * nr + s2] = bt;
-        }
-        continue;
-      }
-      Task t = mk(CHT_U32 | first, k, r, k + 1, dur[2]);
-      t.dep(s_of(k, r));
-      for (int s = 4 * (k + 1); s <= std::min(4 * (k + 1) + 3, rlast); ++s)
-        if (s != r) t.dep(s_of(k, s));
-      if (lu >= 0) t.dep(lu);
-      U[(size_t)k * nr + r] = add(t);
-    }
-    for (int jj = k + 2; jj <= yb; ++jj) {
-      // identity-augmented lists: the corner's columns (jj >= nblk) are read by no later task -- only the
-      // read-out and the gradient use -K^-1 -- so their tiles take deeper groups (chain_group_corner)
-      // (the corner's last updates wait for the last panel solves and form the factorisation's tail: the last
-      // tail_c panels keep depth G)
-      const bool corner = eye && jj >= nblk;
-      const int qlim = corner ? std::max(0, nblk - tail_c) : 0;
-      int q0, q1;
-      if (corner && k < qlim) {
-        q0 = k / Gc * Gc;
-        q1 = std::min(q0 + Gc, qlim);
-      } else {
-        q0 = qlim + (k - qlim) / G * G;
-        q1 = std::min(q0 + G, nblk);
-      }
-      const bool grouped = q1 - q0 > 1 && jj >= q1 + LA;
-      if (grouped && k != q1 - 1) continue;  // the group's one task comes with its last panel
-      // the columns too near the diagonal for the group (chain_group_near > 1): sub-groups of Gn panels of the
-      // group, under the same rule (a column at least LA past the sub-group's last panel), else panel by panel
-      const int p0 = q0 + (k - q0) / Gn * Gn, p1 = std::min(p0 + Gn, q1);
-      const bool sub = !grouped && p1 - p0 > 1 && jj >= p1 + kn.near_la;
-      if (sub && k != p1 - 1) continue;
-      for (int i = jj; i <= yb; ++i) {
-        if (grouped)
-          blk(q0, q1 - q0, i, jj);
-        else if (sub)
-          blk(p0, p1 - p0, i, jj);
-        else
-          blk(k, 1, i, jj);
-      }
-    }
-  }
-  // independent members (a small batch): one copy of the graph per member, tagged in the type word's bits
-  // 8.. (task fields: ty | (g - 1) << 2 | member << 8), scheduled together so that every member's diagonal
-  // chain runs beside the others' tile updates
-  if (nmem > 1) {
-    const int n1 = (int)T.size();
-    T.reserve((size_t)n1 * nmem);
-    for (int m = 1; m < nmem; ++m)
-      for (int t = 0; t < n1; ++t) {
-        Task c = T[t];
-        c.ty |= m << 8;
-        for (int e = 0; e < c.nd; ++e) c.deps[e] += m * n1;
-        T.push_back(c);
-      }
-  }
-  if (overflow) return {};
-  const int n = (int)T.size();
-  // successors in CSR form, each task's in the order its dependants were built
-  std::vector<int> indeg(n, 0), soff(n + 1, 0);
-  for (int t = 0; t < n; ++t)
-    for (int e = 0; e < T[t].nd; ++e) ++soff[T[t].deps[e] + 1];
-  for (int t = 0; t < n; ++t) soff[t + 1] += soff[t];
-  std::vector<int> succ(soff[n]), fill(soff.begin(), soff.end() - 1);
-  for (int t = 0; t < n; ++t)
-    for (int e = 0; e < T[t].nd; ++e) {
-      succ[fill[T[t].deps[e]]++] = t;
-      ++indeg[t];
-    }
-  std::vector<float> bl(n, 0.f);
-  for (int t = n - 1; t >= 0; --t) {  // the construction order is topological
-    float m = 0.f;
-    for (int e = soff[t]; e < soff[t + 1]; ++e) m = std::max(m, bl[succ[e]]);
-    bl[t] = T[t].dur + m;
-  }
-  auto cmp = [&](int a, int b) { return bl[a] != bl[b] ? bl[a] < bl[b] : a > b; };
-  std::priority_queue<int, std::vector<int>, decltype(cmp)> ready(cmp);
-  std::priority_queue<std::pair<float, int>, std::vector<std::pair<float, int>>, std::greater<std::pair<float, int>>> ev;
-  for (int t = 0; t < n; ++t)
-    if (indeg[t] == 0) ready.push(t);
-  std::vector<int32_t> out;
-  out.reserve((size_t)n * 4);
-  int free = std::max(1, grid);
-  float now = 0.f;
-  while ((int)out.size() < 4 * n) {
-    while (free > 0 && !ready.empty()) {
-      const int t = ready.top();
-      ready.pop();
-      out.insert(out.end(), {T[t].ty, T[t].k, T[t].r, T[t].j});
-      ev.push({now + T[t].dur, t});
-      --free;
-    }
-    if (ev.empty()) break;  // (cannot happen for a well-formed graph)
-    const auto e = ev.top();
-    ev.pop();
-    now = e.first;
-    ++free;
-    for (int x = soff[e.second]; x < soff[e.second + 1]; ++x)
-      if (--indeg[succ[x]] == 0) ready.push(succ[x]);
-  }
-  return out;
-}
-
 // chain_kernel applies to one f64 member (or a small batch) without ragged rows -- identity extra rows
 // included (chain_eye) --, on a stream that is not being captured (the first call of a shape uploads its task
 // list), up to chain_max_p (identity rows: chain_max_p_eye) rows; f32 (chain_f32) without identity rows
@@ -892,16 +366,13 @@ int chain_potrf(const gpk_layout* lay, void* W, void* Winv, int32_t* info_dev, c
   const int grid = tn.chain_grid > 0 ? (int)tn.chain_grid : ncu;
   ChainPlan plan;
   int32_t* ctl = nullptr;
-  size_t ctl_ints = 0;
+  const ChainKnobs kn = chain_knobs(tn, lay->n_pad, eye, lay->dtype == GPK_F32, grid);
   {
     std::lock_guard<std::mutex> lk(g_chain_mu);
-    const ChainKnobs kn = chain_knobs(tn, lay->n_pad, eye, lay->dtype == GPK_F32, grid);
     const int nmem = lay->batch;
     // (two lists need workgroups of both roles: at least 8 per XCD)
     const int xcd = tn.chain_xcd != 0 && grid >= 64 ? 1 : 0;
-    auto key = std::make_tuple(dev, lay->n_pad, lay->y_row, grid, nmem, eye ? 1 : 0, kn.group, kn.uq,
-                               kn.group_corner, kn.corner_tail, kn.group_la, xcd, kn.group_near, kn.u128,
-                               kn.near_la, kn.s128);
+    const ChainPlanKey key{dev, lay->n_pad, lay->y_row, grid, nmem, eye ? 1 : 0, xcd, kn};
     auto it = g_chain_plans.find(key);
     if (it == g_chain_plans.end()) {
       std::vector<int32_t> ord = chain_order(lay->n_pad, lay->y_row, grid, nmem, kn, eye);
@@ -920,9 +391,10 @@ int chain_potrf(const gpk_layout* lay, void* W, void* Winv, int32_t* info_dev, c
       it = g_chain_plans.emplace(key, p).first;  // owned for the life of the process
     }
     plan = it->second;
-    ctl_ints = 4 + (size_t)lay->batch * (2 * (size_t)plan.nblk + 2 * (size_t)plan.nblk * plan.nsl + (size_t)plan.nsl * plan.nbc);
-    ctl_ints = (ctl_ints + 3) / 4 * 4;
   }
+  // counters of one member: dflag + hflag per block, sdone + qdone per (block, slice), ucnt per (slice, block column)
+  const size_t ctl_stride = 2 * (size_t)plan.nblk + 2 * (size_t)plan.nblk * plan.nsl + (size_t)plan.nsl * plan.nbc;
+  const size_t ctl_ints = (4 + (size_t)lay->batch * ctl_stride + 3) / 4 * 4;
   {
     auto& c = t_chain_ctl.blocks[{dev, s}];  // this thread's own (see t_chain_ctl)
     if (c.second < ctl_ints) {
@@ -960,8 +432,8 @@ int chain_potrf(const gpk_layout* lay, void* W, void* Winv, int32_t* info_dev, c
   a.nmem = lay->batch;
   a.w_bs = lay->w_batch_stride;
   a.inv_bs = lay->inv_batch_stride;
-  a.ctl_stride = 2 * (int64_t)plan.nblk + 2 * (int64_t)plan.nblk * plan.nsl + (int64_t)plan.nsl * plan.nbc;
-  a.uq = (int32_t)chain_knobs(tn, lay->n_pad, eye, lay->dtype == GPK_F32, grid).uq;
+  a.ctl_stride = (int64_t)ctl_stride;
+  a.uq = (int32_t)kn.uq;
   // rows of L_kk^-1 behind D's early flag: later (more of the panel solve early) for short chains, where the
   // diagonal chain is all there is; earlier for long ones, where the S tasks' waiting CUs cost tile-update time
   // (N = 4096: 112 rows 1.501 vs 96 rows 1.515 ms; 6144 / 8192 2.42 / 4.44 vs 2.37 / 4.39, profiles/r04ab_*)
@@ -975,9 +447,6 @@ int chain_potrf(const gpk_layout* lay, void* W, void* Winv, int32_t* info_dev, c
     }
   if (env_i64("GPK_CHAIN_TIMES", 0)) {
     std::lock_guard<std::mutex> lk(g_chain_mu);
-#ifndef GPK_DIAG_PROF
-#define GPK_DIAG_PROF 0
-#endif
     // (GPK_DIAG_PROF builds: the D tasks' phase stamps follow the task stamps, 8 steps x 8 waves x 6 per block,
     // read back as extra "tasks" of gpk_chain_times)
     const int64_t extra = GPK_DIAG_PROF ? (int64_t)plan.nblk * 8 * 8 : 0;
@@ -1005,13 +474,6 @@ int chain_potrf(const gpk_layout* lay, void* W, void* Winv, int32_t* info_dev, c
 }
 
 }  // namespace
-
-namespace gpk {
-bool tune_asm_feat() { return tune_now().asm_feat != 0; }
-bool tune_asm_f32_fast() { return tune_now().asm_f32_fast != 0; }
-int tune_asm_f32_chunk() { return (int)std::max<int64_t>(1, std::min<int64_t>(64, tune_now().asm_f32_chunk)); }
-bool tune_cp_skip() { return tune_now().cp_skip != 0; }
-}  // namespace gpk
 
 extern "C" {
 
@@ -2471,12 +1933,7 @@ int gpk_tune_thread(const char* key, int64_t value, int32_t set, int64_t* old_va
   if (!key) return fail_arg(1, "key");
   int64_t Tune::*f = knob_field(key);
   if (!f) return fail_arg(1, "key (unknown tuning knob)");
-  auto it = std::find_if(t_tune_over.begin(), t_tune_over.end(),
-                         [&](const std::pair<int64_t Tune::*, int64_t>& o) { return o.first == f; });
-  if (old_set) *old_set = it != t_tune_over.end() ? 1 : 0;
-  if (old_value) *old_value = it != t_tune_over.end() ? it->second : tune().*f;
-  if (it != t_tune_over.end()) t_tune_over.erase(it);
-  if (set) t_tune_over.emplace_back(f, value);
+  tune_thread_set(f, value, set != 0, old_value, old_set);
   return 0;
 }
 

@@ -9,11 +9,9 @@
 #include <utility>
 
 #include "gpk.h"
+#include "gpk_const.h"
 
 namespace gpk {
-
-constexpr int NB = 128;     // panel width == update tile edge == diagonal block edge
-constexpr int ATILE = 64;   // assemble tile edge
 
 // Dynamic LDS above 64 KB needs hipFuncAttributeMaxDynamicSharedMemorySize, which is a per-device
 // attribute of the kernel: raised (never lowered -- one kernel may be launched with several sizes) to the

@@ -840,7 +840,7 @@ hipError_t launch_gemm_t(const GemmArgs& a, int32_t batch, hipStream_t s) {
 // storing wave's vmcnt(0) and a barrier, one lane sets the counter; D, S and U32 read W / Winv with
 // plain loads behind one agent acquire per task.  Every wait is bounded: on timeout
 // the task sets ctl[1] and info = -1 and every workgroup drains the list without work.
-enum { CH_D = 0, CH_S = 1, CH_U32 = 2, CH_BLK = 3 };
+// (the task types CH_D / CH_S / CH_U32 / CH_BLK and the task word's fields: gpk_const.h)
 #ifndef GPK_CHAIN_DEFER_L
 #define GPK_CHAIN_DEFER_L 1  // D publishes L_kk^-1 first and stores L_kk (read by no task of the launch) afterwards
 #endif
@@ -1529,8 +1529,9 @@ __global__ __launch_bounds__(DT) void chain_kernel(ChainArgs a) {
     const int tyg = __builtin_amdgcn_readfirstlane(a.tasks[4 * t]);
     // BLK: updates over g panels; U32 with g > 1: the quarter g - 2 task (UQ); first: the cells the task
     // updates have no earlier update (identity-augmented lists: their counter waits are for 0); member
-    const int ty = tyg & 3, g = ((tyg >> 2) & 15) + 1, first = (tyg >> 6) & 1, mem = tyg >> 8;
-    const bool sq = ty == CH_S && ((tyg >> 7) & 1);  // (chain_uq 2: S + the next block's quarters, chain_sq)
+    const int ty = tyg & kChainTypeMask, g = ((tyg >> kChainGShift) & kChainGMask) + 1;
+    const int first = (tyg >> kChainFirstBit) & 1, mem = tyg >> kChainMemberShift;
+    const bool sq = ty == CH_S && ((tyg >> kChainSqBit) & 1);  // (chain_uq 2: S + the next block's quarters, chain_sq)
     T* const Wm = reinterpret_cast<T*>(a.W) + (int64_t)mem * a.w_bs;
     T* const Wi = reinterpret_cast<T*>(a.Winv) + (int64_t)mem * a.inv_bs;
     const int64_t co = (int64_t)mem * a.ctl_stride;

@@ -614,6 +614,8 @@ int gpk_timing_reset(void);
  * "asm_feat" (1: the K build of a two-leaf SE + periodic tree at D = 4 or 8 computes the per-point features in a
  * pre-pass and runs its interior tiles on the f64 MFMA fast-tile kernel; 0: every tile stages its points itself
  * -- the same bits, slower; A/B).
+ * "diag_debug" (0; timing-only ablation flags of the diagonal-block kernel, never set in production; GPK_DIAG_DEBUG).
+ * "syevj_abs_tol_e3" (0; gpk_syevj: absolute rotation threshold in units of 1e-3 eps max|a_ii|).
  * A persistent launch whose wait timed out
  * sets info = -1 -- an infrastructure failure, not a non-positive pivot: the factorisation is
  * incomplete and W undefined; re-assemble and re-run it with "chain" 0 (the Python layer does,

@@ -17,6 +17,16 @@ def declared_functions():
     return sorted(set(re.findall(r"\b(gpk_[a-z0-9_]+)\s*\(", src)))
 
 
+def table_knobs():
+    """(gpk_tune key, environment name) of every row of the knob table (GPK_KNOBS, csrc/gpk_tune.h): K(field, default)
+    or, where the names do not follow the rule, KN(field, default, "key", "ENVIRONMENT_NAME")."""
+    src = open(os.path.join(_build.CSRC, "gpk_tune.h")).read()
+    src = src[src.index("#define GPK_KNOBS("):src.index("namespace gpk")]
+    rows = [(f, "GPK_" + f.upper()) for f in re.findall(r"^\s*K\((\w+), -?\d+\)", src, flags=re.M)]
+    rows += re.findall(r'^\s*KN\(\w+, -?\d+, "(\w+)", "(\w+)"\)', src, flags=re.M)
+    return rows
+
+
 @pytest.fixture(scope="module")
 def lib():
     _build.build()
@@ -128,16 +138,56 @@ def test_thread_tune_is_per_thread(lib):
 
 
 def test_knob_defaults_land_in_their_fields(lib):
-    """tune() initialises its struct positionally: every knob reads back its documented default (a field
-    inserted out of order shifts the values of the ones after it)."""
+    """Every knob reads back its default -- restated here, not read from the table (gpk_tune.h), so a row that
+    lands in another field or loses its value shows."""
     import os
     expect = {"chain": 1, "chain_max_p": 12416, "chain_grid": 0, "chain_timeout_ms": 1000, "chain_group": 0,
               "chain_max_batch": 8, "chain_batch_max_rows": 17500, "chain_uq": 1, "group": 8, "lookahead": 2,
               "fuse_kbuild": 1, "diag_version": 2, "chain_group_corner": 16, "chain_corner_tail": 8,
               "chain_group_la": 2, "asm_f32_fast": 1, "chain_group_eye": 8, "chain_xcd": 0, "chain_xcd_seats": 16,
-              "asm_f32_chunk": 4, "chain_f32": 1, "chain_group_near": 2, "chain_u128": 2, "chain_near_la": 1, "chain_s128": 2}
+              "asm_f32_chunk": 4, "chain_f32": 1, "chain_group_near": 2, "chain_u128": 2, "chain_near_la": 1, "chain_s128": 2,
+              # the other 24
+              "upd_t128_min": 512, "trsm_t128_min": 256, "diag_debug": 0, "la_min_blocks": 64, "fuse_trsm": 1,
+              "fuse_trsm_max": 256, "reserve_cus": 32, "group_first": 8, "upd_band": 0, "skip_zero_rows": 1,
+              "syevj_abs_tol_e3": 0, "ingroup": 0, "rl_max_tiles": 256, "band_skip": 1, "group_eye": 4,
+              "asm_generic": 0, "panel_stream": 0, "trd_split_m": 1024, "chain_eye": 1,
+              "chain_max_p_eye": 16640, "asm_feat": 1, "chain_min_p": 768, "chain_min_p_eye": 3072, "cp_skip": 1}
+    assert len(expect) == 49 and sorted(expect) == sorted(k for k, _ in table_knobs())
     for k, v in expect.items():
         if os.environ.get("GPK_" + k.upper()):
             continue
         old = _native.tune(k, v)
         assert old == v, (k, old)
+
+
+def test_environment_names_regular_and_irregular(lib):
+    """The environment initialises the knobs under "GPK_" + the key in upper case, and under the name its row
+    states where that differs (diag_dbg: "diag_debug", GPK_DIAG_DEBUG): both read back in a fresh process."""
+    import subprocess
+    import sys
+    assert dict(table_knobs())["chain_group"] == "GPK_CHAIN_GROUP"
+    assert dict(table_knobs())["diag_debug"] == "GPK_DIAG_DEBUG"
+    env = {k: v for k, v in os.environ.items() if not k.startswith("GPK_")}
+    env.update(GPK_CHAIN_GROUP="3", GPK_DIAG_DEBUG="5")
+    code = ("from gaussianprocessfundamentals_amd import _native as n\n"
+            "print([n.tune(k, 0) for k in ('chain_group', 'diag_debug', 'chain_group_eye')])")
+    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, check=True,
+                         cwd=os.path.dirname(HEADER) + "/..")
+    assert out.stdout.strip().splitlines()[-1] == "[3, 5, 8]"
+
+
+def test_every_table_key_is_accepted_and_documented(lib):
+    """The table's keys are exactly the keys gpk.h documents, bar "chain_force_timeout" (no Tune field: the entry
+    point's own), and gpk_tune and gpk_tune_thread accept every one of them."""
+    src = re.sub(r"\s+", " ", open(HEADER).read())
+    doc = src[src.index("Scheduling knobs"):src.index("int gpk_tune(")]
+    documented = set(re.findall(r'"([a-z0-9_]+)"', doc))
+    keys = [k for k, _ in table_knobs()]
+    assert len(keys) == len(set(keys)) == 49
+    assert documented - set(keys) == {"chain_force_timeout"}
+    assert set(keys) - documented == set()
+    for k in keys:
+        old = _native.tune(k, 0)
+        assert _native.tune(k, old) == 0
+        with _native.thread_tune(**{k: 1}):
+            pass

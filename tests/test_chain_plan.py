@@ -582,7 +582,7 @@ def test_chain_plan_eye_reproduces_the_inverse(n, group, uq, rows):
 
 # ------------------------------------------------------------------ two task lists (gpk_tune "chain_xcd")
 def split_lists(tasks):
-    """chain_split_lists (gpk_abi.hip): the diagonal chain's tasks -- D, the panel solves of the next diagonal block's
+    """chain_split_lists (gpk_chain_plan.cpp): the diagonal chain's tasks -- D, the panel solves of the next diagonal block's
     slices, its quarter updates (or per-slice updates) -- to list B, in order; the rest is list A."""
     la, lb = [], []
     for t in tasks:

@@ -463,7 +463,74 @@ class BlockwiseLogLikelihood(AbstractMetric):
             index += nh
         return factor_segments(kernels, slices, dis, noise)
 
+    def _exact(self) -> bool:
+        return (self.local_approx is mht.MatrixApproximations.NONE and
+                self.numerical_matrix_handling is mht.NumericalMatrixHandlingType.CHOLESKY_BASED)
+
+    def _segment_slices(self, hyper_parameter: List):
+        """Per constituent GP: (kernel, [lo, hi) of its entries in ``hyper_parameter``, data input)."""
+        index = blockwise_hyper_parameter_offset(self._gp)
+        out = []
+        for sub in self._gp.constituent_gps:
+            kern = sub.covariance_matrix.kernel
+            nh = kern.get_number_of_hyper_parameter()
+            out.append((kern, index, index + nh, sub.data_input))
+            index += nh
+        return out
+
+    def get_metric_and_gradient(self, hyper_parameter: List, noise, reset: bool = True):
+        """(sum of the segments' -LML [1, 1], [d/d h for h in hyper_parameter] (each shaped like h), d/d noise): the
+        gradient the reference's tape takes through blockwise_LL (LogLikelihood.py:68-104 under
+        Optimizer/Fitter.py:124-158), from ONE ragged identity-augmented device batch
+        (engine.RaggedInverseFactorization: gpk_assemble_inverse_ragged, gpk_potrf_aug_ragged_ex, gpk_grad_ragged).
+
+        Slices follow blockwise_hyper_parameter_offset (always 0, the quirk kept); entries no segment reads get zero
+        gradients; the noise gradient is the sum over the segments in segment order; segments without training points
+        contribute nothing; a segment that is not positive definite makes the value +inf and every gradient NaN.
+        Exact, Cholesky-based likelihood only.  ``reset`` is accepted for the signature of LogLikelihood (the
+        constituents' caches are reset after every evaluation, as get_metric does)."""
+        if not self._exact():
+            raise NotImplementedError(
+                "BlockwiseLogLikelihood gradients are provided for the exact, Cholesky-based likelihood, not for "
+                "%s / %s (gradients of the blockwise approximations are left out)"
+                % (self.local_approx.name, self.numerical_matrix_handling.name))
+        from ..Statistics.CovarianceMatrix import factor_segments_inverse
+        hyper_parameter = list(hyper_parameter)
+        segs = self._segment_slices(hyper_parameter)
+        f, index = factor_segments_inverse([s[0] for s in segs], [hyper_parameter[s[1]:s[2]] for s in segs],
+                                           [s[3] for s in segs], noise, gradient=True)
+        for sub in self._gp.constituent_gps:
+            sub.covariance_matrix.reset()
+            sub.aux.reset()
+        dev = _device()
+        sizes = [max(1, _as_tensor(h).numel()) for h in hyper_parameter]
+        starts = [0]
+        for k in sizes:
+            starts.append(starts[-1] + k)
+        flat = torch.zeros(starts[-1], dtype=torch.float64, device=dev)
+        gnoise = torch.zeros((), dtype=torch.float64, device=dev)
+        if f is None:
+            return torch.zeros((1, 1), dtype=torch.float64, device=dev), _split_like(flat, hyper_parameter), gnoise
+        for b, i in enumerate(index):
+            _, lo, hi, _ = segs[i]
+            g = f.gradient(b)
+            flat[starts[lo]:starts[hi]] += g[:-1]
+            gnoise = gnoise + g[-1]
+        bad = torch.any(f.info != 0)   # (device: no synchronisation)
+        flat = torch.where(bad, torch.full_like(flat, math.nan), flat)
+        gnoise = torch.where(bad, torch.full_like(gnoise, math.nan), gnoise)
+        return torch.sum(f.nlml()).reshape(1, 1), _split_like(flat, hyper_parameter), gnoise
+
+    def get_gradients(self, hyper_parameter: List, noise, reset: bool = True) -> torch.Tensor:
+        """Metrics.py:31: d(sum of -LML)/d(hyperparameters) as one flat vector in the order of ``hyper_parameter``
+        (as LogLikelihood.get_gradients)."""
+        _, grads, _ = self.get_metric_and_gradient(hyper_parameter, noise, reset=reset)
+        return torch.cat([g.reshape(-1) for g in grads]) if grads else torch.zeros(0, dtype=torch.float64)
+
     def get_metric(self, hyper_parameter: List, noise, indices=None, reset: bool = True) -> torch.Tensor:
+        if self._exact() and _wants_grad(hyper_parameter, noise):
+            # differentiable form, as LogLikelihood.get_metric: backward() is the analytic device gradient
+            return _NegLogLikelihood.apply(self, _as_tensor(noise), *[_as_tensor(h) for h in hyper_parameter])
         if (self.local_approx is not mht.MatrixApproximations.NONE or
                 self.numerical_matrix_handling is not mht.NumericalMatrixHandlingType.CHOLESKY_BASED):
             return self._per_segment(hyper_parameter, noise, indices)

@@ -122,25 +122,7 @@ class DeviceLbfgsFitter(GradientFitter):
                  numerical_matrix_handling: mht.NumericalMatrixHandlingType, subset_size: int = None, *,
                  n_starts: int = 8, history: int = 8, max_iter: int = 200, gtol: float = 1e-5, ftol: float = 1e-9,
                  check_every: int = 8, generator: Optional[torch.Generator] = None, bounded: Optional[bool] = None):
-        if isinstance(data_input, list):
-            raise NotImplementedError("DeviceLbfgsFitter: a list of data inputs (k-fold) is not supported")
-        if isinstance(data_input, BatchDataInput):
-            raise NotImplementedError("DeviceLbfgsFitter: BatchDataInput is not supported")
-        if not isinstance(data_input, DataInput):
-            raise NotImplementedError("DeviceLbfgsFitter: data input %s is not supported" % type(data_input).__name__)
-        if metric_type not in (met.MetricType.LL, met.MetricType.BIC):
-            raise NotImplementedError("DeviceLbfgsFitter: metric %s is not supported (LL, BIC)" % metric_type.name)
-        if local_approx is not mht.MatrixApproximations.NONE:
-            raise NotImplementedError("DeviceLbfgsFitter: approximation %s is not supported" % local_approx.name)
-        if numerical_matrix_handling is not mht.NumericalMatrixHandlingType.CHOLESKY_BASED:
-            raise NotImplementedError("DeviceLbfgsFitter: matrix handling %s is not supported (CHOLESKY_BASED)"
-                                      % numerical_matrix_handling.name)
-        from ..MeanFunctionBasics.BaseMeanFunctions import ZeroMeanFunction
-        for owner in (data_input, gaussian_process):
-            mean_function = getattr(owner, "mean_function", None)
-            if mean_function is not None and not isinstance(mean_function, ZeroMeanFunction):
-                raise NotImplementedError("DeviceLbfgsFitter: fitting with the non-zero mean function %s (its "
-                                          "hyperparameters) is not supported" % type(mean_function).__name__)
+        self._check_supported(data_input, gaussian_process, metric_type, local_approx, numerical_matrix_handling)
         if int(n_starts) < 1 or int(check_every) < 1:
             raise ValueError("n_starts and check_every must be >= 1")
         if not 1 <= int(history) <= nat.FIT_MAX_HISTORY:
@@ -155,6 +137,50 @@ class DeviceLbfgsFitter(GradientFitter):
         self.steps = 0
         self.status_reads = 0
 
+    # -- what the class accepts (the k-fold sibling overrides the data-input part) ------------------
+    @classmethod
+    def _check_data_input(cls, data_input):
+        name = cls.__name__
+        if isinstance(data_input, list):
+            raise NotImplementedError("%s: a list of data inputs (k-fold) is not supported" % name)
+        if isinstance(data_input, BatchDataInput):
+            raise NotImplementedError("%s: BatchDataInput is not supported" % name)
+        if not isinstance(data_input, DataInput):
+            raise NotImplementedError("%s: data input %s is not supported" % (name, type(data_input).__name__))
+        return [data_input]
+
+    @classmethod
+    def _check_supported(cls, data_input, gaussian_process, metric_type, local_approx, numerical_matrix_handling):
+        name = cls.__name__
+        inputs = cls._check_data_input(data_input)
+        if metric_type not in (met.MetricType.LL, met.MetricType.BIC):
+            raise NotImplementedError("%s: metric %s is not supported (LL, BIC)" % (name, metric_type.name))
+        if local_approx is not mht.MatrixApproximations.NONE:
+            raise NotImplementedError("%s: approximation %s is not supported" % (name, local_approx.name))
+        if numerical_matrix_handling is not mht.NumericalMatrixHandlingType.CHOLESKY_BASED:
+            raise NotImplementedError("%s: matrix handling %s is not supported (CHOLESKY_BASED)"
+                                      % (name, numerical_matrix_handling.name))
+        from ..MeanFunctionBasics.BaseMeanFunctions import ZeroMeanFunction
+        for owner in inputs + [gaussian_process]:
+            mean_function = getattr(owner, "mean_function", None)
+            if mean_function is not None and not isinstance(mean_function, ZeroMeanFunction):
+                raise NotImplementedError("%s: fitting with the non-zero mean function %s (its "
+                                          "hyperparameters) is not supported" % (name, type(mean_function).__name__))
+
+    # -- hooks of the shared loop: the data behind xrange / n, the batched evaluator, the reported metric ----
+    def _reference_input(self):
+        """The data input whose get_x_range() / n_train size the defaults and the bounds."""
+        return self.data_input
+
+    def _evaluator(self, kernel):
+        """f(cands [S, n_hyp + 1], settle=False) -> (f [S], g [S, n_hyp + 1], info [S]) with .n_par."""
+        from .. import sweep
+        di = self.data_input
+        return sweep.native_batched_value_and_gradient(kernel, di.data_x_train, di.get_detrended_y_train())
+
+    def _metric_value(self, hyper_parameter, noise):
+        return self.metric.get_metric(hyper_parameter, noise)
+
     # -- pieces (host only) ---------------------------------------------------------------------
     def _kernel(self):
         return self._gp.covariance_matrix.kernel
@@ -162,7 +188,8 @@ class DeviceLbfgsFitter(GradientFitter):
     def starts(self) -> torch.Tensor:
         """[n_starts, n_hyp + 1] host tensor: hyperparameters in DFS order, then the noise p_cov_matrix_jitter."""
         kernel = self._kernel()
-        xrange, n = self.data_input.get_x_range(), self.data_input.n_train
+        ref = self._reference_input()
+        xrange, n = ref.get_x_range(), ref.n_train
         jitter = float(torch.as_tensor(global_param.p_cov_matrix_jitter))
         rows = [_flatten(kernel.get_default_hyper_parameter(xrange, n, self.from_distribution)) + [jitter]]
         if self.n_starts > 1:
@@ -180,21 +207,21 @@ class DeviceLbfgsFitter(GradientFitter):
 
     def bounds(self):
         bounded = bool(global_param.p_check_hyper_parameters) if self.bounded is None else bool(self.bounded)
-        return pack_bounds(self._kernel(), self.data_input.get_x_range(), self.data_input.n_train, bounded,
+        ref = self._reference_input()
+        return pack_bounds(self._kernel(), ref.get_x_range(), ref.n_train, bounded,
                            bool(global_param.p_optimize_noise))
 
     # -- the fit ------------------------------------------------------------------------------------
     def fit(self) -> Tuple:
-        from .. import engine, sweep
+        from .. import engine
         kernel = self._kernel()
-        di = self.data_input
         dims = kernel.get_hyper_parameter_dimensionalities()
         x0 = self.starts()
         lo, hi = self.bounds()
         n_par = int(x0.shape[1])
-        pre_fit_metric = self.metric.get_metric(split_winner(x0[0, :-1], dims), x0[0, -1].clone())
+        pre_fit_metric = self._metric_value(split_winner(x0[0, :-1], dims), x0[0, -1].clone())
 
-        evaluate = sweep.native_batched_value_and_gradient(kernel, di.data_x_train, di.get_detrended_y_train())
+        evaluate = self._evaluator(kernel)
         if evaluate.n_par != n_par:
             raise ValueError("the kernel's device program has %d hyperparameters, its defaults %d"
                              % (evaluate.n_par - 1, n_par - 1))
@@ -223,7 +250,7 @@ class DeviceLbfgsFitter(GradientFitter):
                         int(iters[b])) for b in range(self.n_starts)]
         ok = torch.isfinite(fx) & (status != nat.FIT_BAD_START) & (status >= 0)
         if not bool(ok.any()):
-            raise RuntimeError("DeviceLbfgsFitter: no start has a finite objective (%s)" % (self.report,))
+            raise RuntimeError("%s: no start has a finite objective (%s)" % (type(self).__name__, self.report))
         winner = int(torch.argmin(torch.where(ok, fx, torch.full_like(fx, math.inf))))
         self.winner = winner
         self.points = x            # [n_starts, n_hyp + 1]: every start's accepted point (host), the noise last
@@ -232,6 +259,42 @@ class DeviceLbfgsFitter(GradientFitter):
         kernel.set_last_hyper_parameter(hyper_parameter)
         kernel.set_noise(noise)
         last = kernel.get_last_hyper_parameter()
-        post_fit_metric = self.metric.get_metric(last, kernel.get_noise())
+        post_fit_metric = self._metric_value(last, kernel.get_noise())
         # (get_metric records its argument in the kernel, SURVEY Q9: the same list)
         return pre_fit_metric, post_fit_metric, kernel.get_last_hyper_parameter(), kernel.get_noise(), None
+
+
+class DeviceKfoldLbfgsFitter(DeviceLbfgsFitter):
+    """:class:`DeviceLbfgsFitter` for a k-fold list of DataInputs: the objective is the mean of the folds' -LML
+    (the reference's opt_kfold / opt_optimize_noise_kfold, Fitter.py:97-102), evaluated for every start and fold as
+    ONE ragged identity-augmented batch per iteration (sweep.native_kfold_value_and_gradient -> gpk_grad_ragged): folds
+    of Metrics/CrossValidation.get_data_inputs differ in n_train whenever n is not divisible.  The constructor arguments
+    are the sibling's; ``data_input`` is the list.  xrange and n of the defaults and bounds come from fold 0, as
+    upstream (Fitter.py:64-66); the pre- and post-fit metrics are the mean of the folds' ``get_metric``."""
+
+    @classmethod
+    def _check_data_input(cls, data_input):
+        name = cls.__name__
+        if not isinstance(data_input, list) or not data_input:
+            raise NotImplementedError("%s: data_input must be a non-empty list of DataInputs (the folds); a single "
+                                      "data input is DeviceLbfgsFitter's" % name)
+        for fold in data_input:
+            if isinstance(fold, BatchDataInput):
+                raise NotImplementedError("%s: BatchDataInput folds are not supported" % name)
+            if not isinstance(fold, DataInput):
+                raise NotImplementedError("%s: fold of type %s is not supported" % (name, type(fold).__name__))
+            if int(fold.n_train) < 1:
+                raise NotImplementedError("%s: a fold without training points is not supported" % name)
+        return list(data_input)
+
+    def _reference_input(self):
+        return self.data_input[0]
+
+    def _evaluator(self, kernel):
+        from .. import sweep
+        return sweep.native_kfold_value_and_gradient(
+            kernel, [(di.data_x_train, di.get_detrended_y_train()) for di in self.data_input])
+
+    def _metric_value(self, hyper_parameter, noise):
+        values = [m.get_metric(hyper_parameter, noise).reshape(1, 1) for m in self.metric]
+        return torch.mean(torch.stack(values), dim=0)

@@ -302,6 +302,35 @@ def factor_segments(kernels, hyper_parameters, data_inputs, noise, with_test: bo
     return f, index
 
 
+def factor_segments_inverse(kernels, hyper_parameters, data_inputs, noise, gradient: bool = True):
+    """:func:`factor_segments` with identity extra rows (engine.RaggedInverseFactorization): K_i^-1, alpha_i and --
+    ``gradient`` -- d(-LML_i)/d(hyp_i, noise) of every non-empty segment from one ragged device batch.  Returns
+    (factorisation or None, index of the segment behind each batch member).  What the reference's tape differentiates
+    segment by segment through blockwise_LL (gpbasics/Metrics/LogLikelihood.py:68-104 under
+    gpbasics/Optimizer/Fitter.py:124-158)."""
+    if not _is_scalar(noise):
+        raise Exception("Invalid Noise given")
+    members, index = [], []
+    dims = {int(di.data_x_train.shape[1]) for di in data_inputs}
+    if len(dims) != 1:
+        raise ValueError("segments must share the input dimensionality")
+    d = dims.pop()
+    for i, (kern, hyp, di) in enumerate(zip(kernels, hyper_parameters, data_inputs)):
+        if di.n_train == 0:
+            continue
+        kd = engine.kernel_descriptor(kern, d)
+        h = engine.pack_hyper_parameter(hyp, kd.n_hyp)
+        y = di.get_detrended_y_train().reshape(-1).to(torch.float64)
+        members.append((kd, h, di.data_x_train.contiguous(), y))
+        index.append(i)
+        kern._record_hyper_parameter(list(hyp))
+    if not members:
+        return None, index
+    f = engine.RaggedInverseFactorization([int(m[2].shape[0]) for m in members], d, global_param.p_dtype)
+    f.run(members, noise_vector(noise), gradient=gradient)
+    return f, index
+
+
 class SegmentedCovarianceMatrix(CovarianceMatrix):
     """Block-diagonal covariance of a change-point / partition operator whose segments are
     independent local models (CovarianceMatrix.py:289-565).  Every ``get_*_blocks`` returns one

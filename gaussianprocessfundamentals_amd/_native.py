@@ -42,7 +42,11 @@ EXPORTS = (
     "gpk_syevd", "gpk_chain_plan", "gpk_tune_thread", "gpk_chain_stats", "gpk_chain_plan_ex",
     "gpk_op_supported", "gpk_mean_op_supported", "gpk_mean_eval", "gpk_mean_vjp_workspace_bytes", "gpk_mean_vjp",
     "gpk_fit_state_bytes", "gpk_fit_init", "gpk_fit_step", "gpk_fit_current",
+    "gpk_assemble_inverse_ragged", "gpk_potrf_aug_ragged_ex", "gpk_grad_ragged", "gpk_nlml_grad_ragged",
 )
+# the ragged identity-augmented entries (added without a new ABI number, found by symbol)
+RAGGED_GRAD_ENTRIES = ("gpk_assemble_inverse_ragged", "gpk_potrf_aug_ragged_ex", "gpk_grad_ragged",
+                       "gpk_nlml_grad_ragged")
 
 
 class NativeUnavailable(RuntimeError):
@@ -167,9 +171,17 @@ def _declare(lib):
         "gpk_fit_init": (c_int, [c_int, c_int, POINTER(GpkFitOpts), P, c_int64, P, P, P, P, c_int64, P]),
         "gpk_fit_step": (c_int, [c_int, c_int, POINTER(GpkFitOpts), P, c_int64, P, c_int64, P, P, P, c_int64, P, P]),
         "gpk_fit_current": (c_int, [c_int, c_int, P, P, c_int64, P, P, c_int64, P, P]),
+        "gpk_assemble_inverse_ragged": (c_int, [POINTER(GpkKdesc), POINTER(GpkLayout), P, c_int64, P, c_int64,
+                                                P, c_int64, P, c_int64, P, P, P]),
+        "gpk_potrf_aug_ragged_ex": (c_int, [POINTER(GpkLayout), P, P, P, c_int32, P, P, P]),
+        "gpk_grad_ragged": (c_int, [POINTER(GpkKdesc), POINTER(GpkLayout), P, c_int64, P, c_int64, P, P, P, P, P,
+                                    c_size_t, P]),
+        "gpk_nlml_grad_ragged": (c_int, [POINTER(GpkKdesc), POINTER(GpkLayout), P, c_int64, P, c_int64, P, c_int64,
+                                         P, c_int64, P, P, P, P, P, P, P, c_size_t, P]),
     }
     for name, (res, args) in sig.items():
-        if (name == "gpk_op_supported" or name.startswith(("gpk_mean_", "gpk_fit_"))) and not hasattr(lib, name):
+        if (name == "gpk_op_supported" or name in RAGGED_GRAD_ENTRIES or
+                name.startswith(("gpk_mean_", "gpk_fit_"))) and not hasattr(lib, name):
             continue  # (a library built before the entry existed: *op_supported() / fit_supported() then say no)
         fn = getattr(lib, name)
         fn.restype = res
@@ -219,6 +231,14 @@ def fit_supported(library=None) -> bool:
     they existed -- it still loads, and the fitter calls raise NativeUnavailable."""
     L = library if library is not None else load_library()
     return all(hasattr(L, n) for n in ("gpk_fit_state_bytes", "gpk_fit_init", "gpk_fit_step", "gpk_fit_current"))
+
+
+def ragged_grad_supported(library=None) -> bool:
+    """Whether the library has the ragged identity-augmented entries (gpk_assemble_inverse_ragged, gpk_potrf_aug_ragged_ex,
+    gpk_grad_ragged, gpk_nlml_grad_ragged; added without a new ABI number); False for one built before they existed --
+    it still loads, and engine.RaggedInverseFactorization raises NativeUnavailable."""
+    L = library if library is not None else load_library()
+    return all(hasattr(L, n) for n in RAGGED_GRAD_ENTRIES)
 
 
 def fit_state_bytes(n_par: int, batch: int, opts: "GpkFitOpts" = None) -> int:

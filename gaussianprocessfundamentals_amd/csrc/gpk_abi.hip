@@ -1157,6 +1157,92 @@ int gpk_nlml_grad(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_
   return 0;
 }
 
+// ---------------------------------------------------------------- ragged identity-augmented batches
+// Members of different sizes with identity extra rows: member b's extra rows t < n_b are e_t, the rest zero rows
+// (m_b = n_b), its training rows past n_b identity padding.  assemble_impl, potrf_impl and finalize_impl take both
+// modes at once; the gradient pass reads n_b per member (grad_kernel's ragged instantiation).
+int gpk_assemble_inverse_ragged(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_dev,
+                                int64_t hyp_stride, const double* noise_dev, int64_t noise_stride,
+                                const double* X, int64_t x_bstride, const double* y, int64_t y_bstride,
+                                const int64_t* n_dev, void* W, void* stream) {
+  if (!n_dev) return fail_arg(11, "n_dev");
+  return assemble_impl(kd, lay, hyp_dev, hyp_stride, noise_dev, noise_stride, X, x_bstride, nullptr, 0, nullptr, 0,
+                       y, y_bstride, W, true, n_dev, n_dev, stream);
+}
+
+int gpk_potrf_aug_ragged_ex(const gpk_layout* lay, void* W, void* Winv, int32_t* info_dev, int32_t flags,
+                            const int64_t* n_dev, const int64_t* m_dev, void* stream) {
+  if (!n_dev) return fail_arg(6, "n_dev");
+  if (lay && lay->m > 0 && !m_dev) return fail_arg(7, "m_dev (layout planned with m > 0)");
+  return potrf_impl(lay, W, Winv, info_dev, flags, n_dev, lay && lay->m > 0 ? m_dev : nullptr, stream);
+}
+
+int gpk_grad_ragged(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_dev, int64_t hyp_stride,
+                    const double* X, int64_t x_bstride, const int64_t* n_dev, const void* W,
+                    const int32_t* info_dev, double* grad_dev, void* work, size_t work_bytes, void* stream) {
+  if (int e = check_layout(lay)) return e == -1 ? fail_arg(2, "layout (use gpk_plan)") : e;
+  if (lay->m != lay->n) return fail_arg(2, "gpk_grad_ragged needs a layout planned with m = n");
+  if (!valid_kdesc(kd, lay->d)) return fail_arg(1, "kernel descriptor");
+  if (!hyp_dev && kd->n_hyp > 0) return fail_arg(3, "hyp_dev");
+  if (!X) return fail_arg(5, "X");
+  if (!n_dev) return fail_arg(7, "n_dev");
+  if (!W) return fail_arg(8, "W");
+  if (!info_dev) return fail_arg(9, "info_dev");
+  if (!grad_dev) return fail_arg(10, "grad_dev");
+  if (!work || work_bytes < gpk_grad_workspace_bytes(kd, lay))
+    return fail_arg(11, "work (see gpk_grad_workspace_bytes)");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  GradArgs g;
+  memset(&g, 0, sizeof(g));
+  g.W = W;
+  g.ld = lay->ld;
+  g.w_bs = lay->w_batch_stride;
+  g.n = lay->n;
+  g.n_pad = lay->n_pad;
+  g.y_row = lay->y_row;
+  g.hyp = hyp_dev;
+  g.hyp_stride = hyp_stride;
+  g.X = X;
+  g.x_bs = x_bstride;
+  g.d = (int32_t)lay->d;
+  g.dp = (lay->d % 2 == 0) ? (int32_t)lay->d + 1 : (int32_t)lay->d;
+  g.ntile = (lay->n + ATILE - 1) / ATILE;
+  g.part = static_cast<double*>(work);
+  g.grad = grad_dev;
+  g.info = info_dev;
+  g.nb = n_dev;
+  adjoint_masks(*kd, g.adj_mask);
+  GPK_HIP(timed(6, 0.0, 0.0, s, [&] { return launch_grad(*kd, g, lay->dtype, lay->batch, s); }), "grad");
+  return 0;
+}
+
+int gpk_nlml_grad_ragged(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_dev, int64_t hyp_stride,
+                         const double* noise_dev, int64_t noise_stride, const double* X, int64_t x_bstride,
+                         const double* y, int64_t y_bstride, const int64_t* n_dev, void* W, void* Winv,
+                         int32_t* info_dev, double* out_dev, double* grad_dev, void* work, size_t work_bytes,
+                         void* stream) {
+  if (int e = check_layout(lay)) return e == -1 ? fail_arg(2, "layout (use gpk_plan)") : e;
+  if (lay->m != lay->n) return fail_arg(2, "gpk_nlml_grad_ragged needs a layout planned with m = n");
+  if (!valid_kdesc(kd, lay->d)) return fail_arg(1, "kernel descriptor");
+  if (!n_dev) return fail_arg(11, "n_dev");
+  if (!info_dev) return fail_arg(14, "info_dev");
+  if (!out_dev) return fail_arg(15, "out_dev");
+  if (grad_dev && (!work || work_bytes < gpk_grad_workspace_bytes(kd, lay)))
+    return fail_arg(17, "work (see gpk_grad_workspace_bytes)");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  GPK_HIP(hipMemsetAsync(info_dev, 0, sizeof(int32_t) * lay->batch, s), "memset info");
+  int e = gpk_assemble_inverse_ragged(kd, lay, hyp_dev, hyp_stride, noise_dev, noise_stride, X, x_bstride, y,
+                                      y_bstride, n_dev, W, stream);
+  if (e) return e;
+  e = gpk_potrf_aug_ragged_ex(lay, W, Winv, info_dev, GPK_AUG_EXTRA_IDENTITY, n_dev, n_dev, stream);
+  if (e) return e;
+  e = gpk_finalize_ragged(lay, W, info_dev, n_dev, out_dev, nullptr, nullptr, stream);
+  if (e) return e;
+  if (!grad_dev) return 0;
+  return gpk_grad_ragged(kd, lay, hyp_dev, hyp_stride, X, x_bstride, n_dev, W, info_dev, grad_dev, work, work_bytes,
+                         stream);
+}
+
 int gpk_kernel_matrix(const gpk_kdesc* kd, const double* hyp_dev, int dtype, int uplo,
                       const double* X, int64_t n, const double* Y, int64_t m, int32_t d,
                       double diag_add, void* K, int64_t ldk, void* stream) {

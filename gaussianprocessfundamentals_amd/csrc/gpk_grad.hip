@@ -224,7 +224,20 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;
 }
 
-template <typename T, bool RQL>
+// training points of member b: the batch's one n, or (RAG) the member's own.  Spelled as a read of g.n at every use in
+// the uniform instantiations, as before the ragged ones existed: a local copy of it changed their code.
+template <bool RAG>
+__device__ __forceinline__ int64_t grad_member_n(const GradArgs& g, int b) {
+  if constexpr (RAG) return g.nb[b];
+  else return g.n;
+}
+
+// RAG: the ragged instantiation (gpk_grad_ragged) -- member b's own n_b = g.nb[b] bounds the alpha staging, qval and
+// (through a.nb, member_n) the points staged; a tile wholly at or beyond n_b writes its n_hyp + 1 partial sums as
+// plain zeros and evaluates nothing (the workspace is not cleared and grad_reduce_kernel sums every tile of the layout,
+// a window leaf's shared bound included: no read-modify-write of an unwritten slot).  The tile index t does not depend
+// on n, so a member's nonzero partials sit where they do when it is factored alone.
+template <typename T, bool RQL, bool RAG = false>
 __global__ __launch_bounds__(256) void grad_kernel(gpk_kdesc kd, AsmArgs a, GradArgs g) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int slot_stride = ATILE * a.dp;
@@ -247,6 +260,12 @@ __global__ __launch_bounds__(256) void grad_kernel(gpk_kdesc kd, AsmArgs a, Grad
   const int np1 = kd.n_hyp + 1;
   double* part = g.part + ((int64_t)b * gridDim.x + t) * np1;
 
+  if constexpr (RAG) {
+    if (ti * ATILE >= grad_member_n<RAG>(g, b)) {  // (tj <= ti: a lower tile whose rows are padding has no element below n_b; workgroup-uniform)
+      for (int e = tid; e < np1; e += 256) part[e] = 0.0;
+      return;
+    }
+  }
   const double* hyp_g = g.hyp + (int64_t)b * g.hyp_stride;
   for (int e = tid; e < kd.n_hyp; e += 256) hyp_s[e] = hyp_g[e];
   const T* W = reinterpret_cast<const T*>(g.W) + (int64_t)b * g.w_bs;
@@ -254,7 +273,7 @@ __global__ __launch_bounds__(256) void grad_kernel(gpk_kdesc kd, AsmArgs a, Grad
   if (tid < 2 * ATILE) {
     const int64_t gg = (tid < ATILE ? gi0 : gj0) + (tid & (ATILE - 1));
     // y row of the corner: -alpha^T
-    const double v = gg < g.n ? -(double)W[g.y_row * g.ld + g.n_pad + gg] : 0.0;
+    const double v = gg < grad_member_n<RAG>(g, b) ? -(double)W[g.y_row * g.ld + g.n_pad + gg] : 0.0;
     (tid < ATILE ? al_r : al_c)[tid & (ATILE - 1)] = v;
   }
   __syncthreads();
@@ -268,7 +287,7 @@ __global__ __launch_bounds__(256) void grad_kernel(gpk_kdesc kd, AsmArgs a, Grad
   // (the strictly lower triangle stands for both halves), 1 on it; the corner holds -K^-1
   auto qval = [&](int rr) -> double {
     const int64_t gi = gi0 + rr;
-    if (gi >= g.n || gj > gi) return 0.0;
+    if (gi >= grad_member_n<RAG>(g, b) || gj > gi) return 0.0;
     const double qq = -(double)W[(g.n_pad + gi) * g.ld + g.n_pad + gj] - al_r[rr] * al_c[c];
     return gi == gj ? qq : 2.0 * qq;
   };
@@ -644,6 +663,8 @@ hipError_t launch_grad(const gpk_kdesc& kd, const GradArgs& g, int dtype, int32_
   a.d = g.d;
   a.dp = g.dp;
   a.eye = 1;
+  a.nb = g.nb;  // ragged (NULL: uniform): member_n / member_m bound the points stage_points reads (m_b = n_b)
+  a.mb = g.nb;
   const int64_t ntri = g.ntile * (g.ntile + 1) / 2;
   bool has_mul = false;
   for (int q = 0; q < kd.n_nodes; ++q) has_mul |= g.adj_mask[q] != 0u;
@@ -653,8 +674,12 @@ hipError_t launch_grad(const gpk_kdesc& kd, const GradArgs& g, int dtype, int32_
   dim3 grid((unsigned)ntri, (unsigned)batch, 1);
   // (a program with a rational quadratic leaf: the instantiation that carries the leaf's code, rq_leaves)
   const bool rq = rq_leaves(kd) > 0;
-  const auto grad = dtype == GPK_F64 ? (rq ? grad_kernel<double, true> : grad_kernel<double, false>)
-                                     : (rq ? grad_kernel<float, true> : grad_kernel<float, false>);
+  const auto grad =
+      g.nb != nullptr
+          ? (dtype == GPK_F64 ? (rq ? grad_kernel<double, true, true> : grad_kernel<double, false, true>)
+                              : (rq ? grad_kernel<float, true, true> : grad_kernel<float, false, true>))
+          : (dtype == GPK_F64 ? (rq ? grad_kernel<double, true> : grad_kernel<double, false>)
+                              : (rq ? grad_kernel<float, true> : grad_kernel<float, false>));
   {
     hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(grad), lds);
     if (e != hipSuccess) return e;

@@ -229,6 +229,8 @@ struct GradArgs {
   double* grad;        // [batch][n_hyp + 1]
   const int32_t* info;
   uint32_t adj_mask[GPK_MAX_NODES];  // per node: nodes whose values multiply its adjoint
+  const int64_t* nb;   // ragged batches (gpk_grad_ragged): training points of member b (NULL: n); last, so that the
+                       // uniform instantiations read every other field where they did
 };
 
 // gpk_kernel_vjp (gpk_grad.hip): adjoints of K(X, Z) = kernel(X, Z) for a weight matrix G [n, ldg]

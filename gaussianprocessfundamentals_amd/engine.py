@@ -776,6 +776,184 @@ class RaggedFactorization(AugmentedFactorization):
         return self.alphas()[b]
 
 
+def program_runs(kds: Sequence) -> List[tuple]:
+    """Maximal runs (start, stop) of consecutive members whose device programs are byte-identical: each run is one
+    launch of the per-program passes (K build, gradient) of a ragged batch."""
+    runs, b0 = [], 0
+    for b in range(1, len(kds) + 1):
+        if b == len(kds) or bytes(kds[b]) != bytes(kds[b0]):
+            runs.append((b0, b))
+            b0 = b
+    return runs
+
+
+class RaggedInverseFactorization(AugmentedFactorization):
+    """Identity-augmented factorisation (+ -LML gradient) of independent problems of DIFFERENT sizes: the sibling of
+    :class:`RaggedFactorization` for what :class:`InverseFactorization` computes (gpk_assemble_inverse_ragged,
+    gpk_potrf_aug_ragged_ex, gpk_finalize_ragged, gpk_grad_ragged).
+
+    The layout is planned with m = n = max(sizes).  Member b's training rows past ``sizes[b]`` are identity padding,
+    its extra rows t < sizes[b] are e_t and the rest zero rows; after :meth:`run` its corner holds -K_b^-1, the
+    corner's y row -alpha_b^T and its extra rows L_b^-T.  This serves the gradient of the reference's blockwise_LL
+    (gpbasics/Metrics/LogLikelihood.py:68-104 under the tape of gpbasics/Optimizer/Fitter.py:124-158), the k-fold
+    objective (Fitter.py:97-102) and the per-segment inverses of SegmentedCovarianceMatrix
+    (gpbasics/Statistics/CovarianceMatrix.py:520-556) with ONE panel chain for all members.
+
+    Consecutive members sharing a device program are assembled and differentiated by one launch (a batch layout with
+    offset pointers), the others by a launch each; the factorisation and the read-out are always one set of launches.
+    """
+
+    def __init__(self, sizes: Sequence[int], d: int, dtype=None):
+        sizes = [int(s) for s in sizes]
+        if not sizes or min(sizes) < 1:
+            raise ValueError("every member of a ragged batch needs at least one training point")
+        if not nat.ragged_grad_supported():
+            raise nat.NativeUnavailable("this libgpk.so was built before the ragged identity-augmented entries "
+                                        "(gpk_grad_ragged and its kin) existed: rebuild it")
+        super().__init__(max(sizes), d, max(sizes), len(sizes), dtype)
+        self.sizes = sizes
+        self.n_dev = torch.tensor(sizes, dtype=torch.int64, device=self.W.device)
+        self.grad = None
+        self.work = None
+
+    def run(self, members: Sequence, noise, gradient: bool = True) -> "RaggedInverseFactorization":
+        """members[b] = (kdesc, hyp [n_hyp] fp64, X_b [n_b, d], y_b [n_b]); noise: rank-0 or one value per member.
+        Asynchronous; ``gradient()`` / ``nlml()`` are device tensors."""
+        B, n, d = self.batch, self.n, self.d
+        if len(members) != B:
+            raise ValueError("expected %d members, got %d" % (B, len(members)))
+        dev = self.W.device
+        X = torch.zeros((B, n, d), dtype=torch.float64, device=dev)
+        y = torch.zeros((B, n), dtype=torch.float64, device=dev)
+        hyp = torch.zeros((B, nat.MAX_HYP), dtype=torch.float64, device=dev)
+        kds = []
+        for b, (kd, h, xb, yb) in enumerate(members):
+            nb = self.sizes[b]
+            if tuple(xb.shape) != (nb, d) or yb.numel() != nb:
+                raise ValueError("member %d: X must be [%d, %d] and y hold %d values" % (b, nb, d, nb))
+            if h.numel() != kd.n_hyp:
+                raise ValueError("member %d: %d hyperparameters, kernel expects %d" % (b, h.numel(), kd.n_hyp))
+            X[b, :nb] = xb.detach()
+            y[b, :nb] = yb.detach().reshape(-1)
+            hyp[b, :kd.n_hyp] = h.detach().reshape(-1)
+            kds.append(kd)
+        nz = noise if isinstance(noise, torch.Tensor) else torch.as_tensor(noise, dtype=torch.float64)
+        nz = nz.detach().to(device=dev, dtype=torch.float64).reshape(-1)
+        nz = (nz.expand(B) if nz.numel() == 1 else nz).contiguous()
+        if nz.numel() != B:
+            raise ValueError("noise must be rank-0 or hold one value per member")
+        return self.run_packed(kds, hyp, nz, X, y, gradient)
+
+    def run_packed(self, kds: Sequence, hyp: torch.Tensor, noise: torch.Tensor, X: torch.Tensor, y: torch.Tensor,
+                   gradient: bool = True) -> "RaggedInverseFactorization":
+        """:meth:`run` on operands already packed on the device: hyp [B, MAX_HYP], noise [B], X [B, n, d] and
+        y [B, n] (zero-filled past each member's size), kds one program per member.  No host round trip."""
+        self._pending = None
+        self._alphas = None
+        B, n, d = self.batch, self.n, self.d
+        dev = self.W.device
+        if len(kds) != B:
+            raise ValueError("expected %d programs, got %d" % (B, len(kds)))
+        _check_operand("hyper_parameter", hyp, nat.MAX_HYP, nat.MAX_HYP, B, dev)
+        _check_operand("noise", noise, 1, 1, B, dev)
+        _check_operand("X", X, n * d, n * d, B, dev)
+        _check_operand("y", y, n, n, B, dev)
+        self._fresh_out()
+        L, s, lay = self.L, nat.stream_handle(dev), self.layout
+        runs = program_runs(kds)
+        lays = {}
+
+        def sub_layout(count):   # same p / ld / strides as the batched layout
+            if count not in lays:
+                lays[count] = lay if count == B else nat.plan(self.code, count, n, n, d)
+            return lays[count]
+
+        self.info.zero_()
+        for b0, b1 in runs:
+            nat.check(L.gpk_assemble_inverse_ragged(
+                ctypes.byref(kds[b0]), ctypes.byref(sub_layout(b1 - b0)), _offset_ptr(hyp, b0 * nat.MAX_HYP),
+                nat.MAX_HYP, _offset_ptr(noise, b0), 1, _offset_ptr(X, b0 * n * d), n * d, _offset_ptr(y, b0 * n), n,
+                _offset_ptr(self.n_dev, b0), _offset_ptr(self._W, b0 * lay.w_batch_stride), s),
+                "gpk_assemble_inverse_ragged")
+        nat.check(L.gpk_potrf_aug_ragged_ex(ctypes.byref(lay), nat.ptr(self._W), nat.ptr(self._Winv),
+                                            nat.ptr(self._info), nat.AUG_EXTRA_IDENTITY, nat.ptr(self.n_dev),
+                                            nat.ptr(self.n_dev), s), "gpk_potrf_aug_ragged_ex")
+        nat.check(L.gpk_finalize_ragged(ctypes.byref(lay), nat.ptr(self._W), nat.ptr(self._info),
+                                        nat.ptr(self.n_dev), nat.ptr(self._out), None, None, s),
+                  "gpk_finalize_ragged")
+        self.grad = self._grads = None
+        if gradient:
+            # one workspace for every run (sized for the run that needs most; the runs follow each other on the stream)
+            need = max(int(L.gpk_grad_workspace_bytes(ctypes.byref(kds[b0]), ctypes.byref(sub_layout(b1 - b0))))
+                       for b0, b1 in runs)
+            if self.work is None or self.work.numel() * 8 < need:
+                self.work = torch.empty(max(1, need // 8), dtype=torch.float64, device=dev)
+            self._grads = []
+            for b0, b1 in runs:
+                kd, sl = kds[b0], sub_layout(b1 - b0)
+                g = torch.empty((b1 - b0, kd.n_hyp + 1), dtype=torch.float64, device=dev)
+                nat.check(L.gpk_grad_ragged(
+                    ctypes.byref(kd), ctypes.byref(sl), _offset_ptr(hyp, b0 * nat.MAX_HYP), nat.MAX_HYP,
+                    _offset_ptr(X, b0 * n * d), n * d, _offset_ptr(self.n_dev, b0),
+                    _offset_ptr(self._W, b0 * lay.w_batch_stride), _offset_ptr(self._info, b0), nat.ptr(g),
+                    nat.ptr(self.work), self.work.numel() * 8, s), "gpk_grad_ragged")
+                self._grads.append(g)
+            self.grad = self._grads[0] if len(runs) == 1 else None
+            self._runs = runs
+        self._keep = (X, y, hyp, noise)  # operands stay alive until the stream has consumed them
+        self.kd = list(kds)
+        self.done = True
+        return self
+
+    # -- per-member read-out (device views, no host synchronisation) ---------------------------
+    def gradients(self) -> torch.Tensor:
+        """[B, n_hyp + 1] of a batch whose members share one program (the k-fold case)."""
+        if getattr(self, "_grads", None) is None or self.grad is None:
+            raise RuntimeError("run(..., gradient=True) on members sharing one program first")
+        return self.grad
+
+    def gradient(self, b: int) -> torch.Tensor:
+        """[n_hyp_b + 1] fp64: d(-LML_b)/d hyp (DFS order), then d(-LML_b)/d noise; NaN where info[b] != 0."""
+        if getattr(self, "_grads", None) is None:
+            raise RuntimeError("run(..., gradient=True) first")
+        for (b0, b1), g in zip(self._runs, self._grads):
+            if b0 <= b < b1:
+                return g[b - b0]
+        raise IndexError(b)
+
+    def corner(self, b: int = 0) -> torch.Tensor:
+        lay, nb = self.layout, self.sizes[b]
+        c = self.w(b)[lay.n_pad:lay.n_pad + nb, lay.n_pad:lay.n_pad + nb]
+        return torch.tril(c) + torch.tril(c, -1).transpose(0, 1)
+
+    def k_inv(self, b: int = 0) -> torch.Tensor:
+        """(K_b + noise I)^-1 [n_b, n_b], symmetrised from the corner's lower triangle."""
+        return -self.corner(b)
+
+    def extra_rows(self, b: int = 0) -> torch.Tensor:
+        lay, nb = self.layout, self.sizes[b]
+        return self.w(b)[lay.n_pad:lay.n_pad + nb, :nb]
+
+    def l_inv(self, b: int = 0) -> torch.Tensor:
+        """L_b^-1 (lower): the transpose of the extra rows, which hold L_b^-T."""
+        return torch.triu(self.extra_rows(b)).transpose(0, 1)
+
+    def cholesky(self, b: int = 0) -> torch.Tensor:
+        nb = self.sizes[b]
+        return torch.tril(self.w(b)[:nb, :nb])
+
+    def z(self, b: int = 0) -> torch.Tensor:
+        return self.w(b)[self.layout.y_row, :self.sizes[b]]
+
+    def alpha(self, b: int = 0) -> torch.Tensor:
+        """alpha_b [n_b], read from the corner's y row."""
+        lay = self.layout
+        return -self.w(b)[lay.y_row, lay.n_pad:lay.n_pad + self.sizes[b]].to(torch.float64)
+
+    def alphas(self):
+        return [self.alpha(b) for b in range(self.batch)]
+
+
 def gemv(A: torch.Tensor, x: torch.Tensor, y: Optional[torch.Tensor] = None, alpha: float = 1.0,
          beta: float = 0.0) -> torch.Tensor:
     """y <- alpha A x + beta y on the device (gpk_gemv; A row-major fp64 [n, m], x [m] or [m, 1]).

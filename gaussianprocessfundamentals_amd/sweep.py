@@ -152,6 +152,88 @@ def native_batched_value_and_gradient(kernel, X: torch.Tensor, y: torch.Tensor, 
     return evaluate
 
 
+def replicate_candidates(cands: torch.Tensor, n_folds: int, width: int):
+    """Candidate rows [S, n_hyp + 1] (the noise last) -> (hyp [S * F, width] zero-filled past n_hyp, noise [S * F]):
+    member s * F + f is candidate s on fold f.  Tensor ops on the candidates' device only (no host round trip)."""
+    S, n_hyp = int(cands.shape[0]), int(cands.shape[1]) - 1
+    hyp = torch.zeros((S * n_folds, width), dtype=cands.dtype, device=cands.device)
+    hyp[:, :n_hyp] = cands[:, :n_hyp].repeat_interleave(n_folds, dim=0)
+    noise = cands[:, n_hyp].repeat_interleave(n_folds).contiguous()
+    return hyp, noise
+
+
+def fold_mean(values: torch.Tensor, n_folds: int) -> torch.Tensor:
+    """Mean over the folds of per-member values [S * F] or [S * F, k] (member s * F + f): the folds are added in fold
+    order, one after the other, then divided by F -- a fixed order, the same bits on every call."""
+    v = values.reshape((-1, n_folds) + tuple(values.shape[1:]))
+    acc = v[:, 0]
+    for f in range(1, n_folds):
+        acc = acc + v[:, f]
+    return acc / float(n_folds)
+
+
+def fold_info(info: torch.Tensor, n_folds: int) -> torch.Tensor:
+    """[S] int32: non-zero where any fold's info is (the largest magnitude among the candidate's folds)."""
+    return info.reshape(-1, n_folds).abs().amax(dim=1).to(torch.int32)
+
+
+def native_kfold_value_and_gradient(kernel, folds, dtype=None):
+    """Mean over k folds of -LML and of its gradient for a batch of (hyperparameters, noise) candidates: the reference's
+    opt_kfold / opt_optimize_noise_kfold objective (gpbasics/Optimizer/Fitter.py:97-102) under its tape, as ONE ragged
+    identity-augmented batch of S * F members per call (engine.RaggedInverseFactorization -> gpk_grad_ragged).  The
+    folds of Metrics/CrossValidation.get_data_inputs differ in n_train whenever n is not divisible by k, which a uniform
+    batch cannot take.
+
+    ``folds``: a list of (X_f [n_f, d], y_f [n_f]).  Returns f(cands [S, n_hyp + 1] fp64 on the device, the noise last)
+    -> (f [S], g [S, n_hyp + 1], info [S] int32): device tensors; f is +inf and g NaN where any fold's factorisation
+    failed (info non-zero).  Candidate rows are replicated to the members on the device (:func:`replicate_candidates`)
+    and the folds reduced in a fixed order (:func:`fold_mean`).  The call only enqueues: no host synchronisation
+    (``settle`` is accepted for the signature of native_batched_value_and_gradient: ragged batches never take the
+    persistent launch, so there is nothing to verify)."""
+    from . import _native as nat
+    folds = [(engine.as_device_f64(X), engine.as_device_f64(y).reshape(-1)) for X, y in folds]
+    if not folds:
+        raise ValueError("at least one fold is needed")
+    F = len(folds)
+    d = int(folds[0][0].shape[1])
+    sizes = []
+    for X, y in folds:
+        if X.dim() != 2 or int(X.shape[1]) != d or int(y.numel()) != int(X.shape[0]) or int(X.shape[0]) < 1:
+            raise ValueError("every fold needs X [n_f >= 1, %d] and y with n_f values" % d)
+        sizes.append(int(X.shape[0]))
+    n = max(sizes)
+    dev = folds[0][0].device
+    kd = engine.kernel_descriptor(kernel, d)
+    width = kd.n_hyp + 1
+    dt = dtype or gp.p_dtype
+    Xf = torch.zeros((F, n, d), dtype=torch.float64, device=dev)
+    yf = torch.zeros((F, n), dtype=torch.float64, device=dev)
+    for k, (X, y) in enumerate(folds):
+        Xf[k, :sizes[k]] = X
+        yf[k, :sizes[k]] = y
+    cache = {}
+
+    def evaluate(cands: torch.Tensor, settle: bool = False):
+        if cands.dim() != 2 or int(cands.shape[1]) != width:
+            raise ValueError("candidate rows must have %d values (hyperparameters, then the noise)" % width)
+        if cands.dtype != torch.float64 or cands.device != dev or not cands.is_contiguous():
+            raise ValueError("candidates must be a contiguous float64 tensor on %s" % (dev,))
+        S = int(cands.shape[0])
+        slot = cache.get(S)
+        if slot is None:
+            fac = engine.RaggedInverseFactorization(sizes * S, d, dt)
+            slot = cache[S] = (fac, Xf.repeat(S, 1, 1).contiguous(), yf.repeat(S, 1).contiguous(), [kd] * (S * F))
+        fac, Xp, yp, kds = slot
+        hyp, noise = replicate_candidates(cands, F, nat.MAX_HYP)
+        fac.run_packed(kds, hyp, noise, Xp, yp, gradient=True)
+        return (fold_mean(fac._out.view(S * F, 4)[:, 0], F), fold_mean(fac.gradients(), F),
+                fold_info(fac._info, F))
+
+    evaluate.n_par = width
+    evaluate.n_folds = F
+    return evaluate
+
+
 class HyperparameterSweep:
     """Evaluate -LML for every row of a candidate matrix across the ranks of ``group``.
 

@@ -242,6 +242,43 @@ int gpk_nlml_ragged(const gpk_kdesc* kd, const gpk_layout* lay, const double* hy
                     const double* y, int64_t y_bstride, const int64_t* n_dev, void* W, void* Winv,
                     int32_t* info_dev, double* out_dev, void* stream);
 
+/* Ragged identity-augmented batches: -LML, K^-1, alpha and the gradient of members of different sizes from one set
+ * of launches (entries added without a new ABI number, found by symbol like gpk_op_supported).  The layout is
+ * planned with m = n = max n_b.  Member b uses its first n_dev[b] points; its training rows n_dev[b] .. n_pad-1
+ * are identity padding as in gpk_assemble_ragged, its extra rows t < n_dev[b] are e_t and its extra rows
+ * t >= n_dev[b] zero rows (m_b = n_b), which the factorisation skips like unused test rows.  After the
+ * factorisation member b's corner holds -K_b^-1 in its first n_b rows and columns and its y row -alpha_b^T.
+ *
+ * gpk_assemble_inverse_ragged: gpk_assemble_inverse per member -- the K build of the per-segment inverses of
+ *   SegmentedCovarianceMatrix.get_K_inv_blocks / get_L_inv_K_blocks (Statistics/CovarianceMatrix.py:520-556).
+ *   Errors: -11 n_dev NULL, -2 layout planned with m != n, -1 invalid layout or kernel program.
+ * gpk_potrf_aug_ragged_ex: gpk_potrf_aug_ragged with flags (GPK_AUG_EXTRA_IDENTITY: m_dev[b] = n_dev[b]); always
+ *   the launch path (the persistent launch takes no ragged members).  Errors: -6 n_dev NULL, -7 m_dev NULL with
+ *   m > 0, -5 unknown flags, -1 invalid layout or identity rows with m != n.
+ * gpk_grad_ragged: the gradient pass alone on a factored identity-augmented W, for members that share one kernel
+ *   program: grad_dev[b*(n_hyp+1) + p] as gpk_nlml_grad writes it (NaN where info_dev[b] != 0) -- the derivative the
+ *   reference's tape takes through blockwise_LL and through the mean of the folds' metrics (Optimizer/Fitter.py:97-102,
+ *   :124-158; Metrics/LogLikelihood.py:68-104).  work: gpk_grad_workspace_bytes(kd, lay) bytes (the layout holds the
+ *   largest member).  Errors: -7 n_dev NULL, -2 layout invalid or planned with m != n, -1 invalid kernel program,
+ *   -11 work NULL or too small; -3, -5, -8, -9, -10 the other NULL pointers.
+ * gpk_nlml_grad_ragged: memset of info + the three calls above + gpk_finalize_ragged, the ragged twin of
+ *   gpk_nlml_grad; grad_dev == NULL gives value and inverse only.  Errors: -11 n_dev NULL, -2 layout invalid or
+ *   planned with m != n, -1 invalid kernel program, -14 info_dev, -15 out_dev, -17 work NULL or too small. */
+int gpk_assemble_inverse_ragged(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_dev,
+                                int64_t hyp_stride, const double* noise_dev, int64_t noise_stride,
+                                const double* X, int64_t x_bstride, const double* y, int64_t y_bstride,
+                                const int64_t* n_dev, void* W, void* stream);
+int gpk_potrf_aug_ragged_ex(const gpk_layout* lay, void* W, void* Winv, int32_t* info_dev, int32_t flags,
+                            const int64_t* n_dev, const int64_t* m_dev, void* stream);
+int gpk_grad_ragged(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_dev, int64_t hyp_stride,
+                    const double* X, int64_t x_bstride, const int64_t* n_dev, const void* W,
+                    const int32_t* info_dev, double* grad_dev, void* work, size_t work_bytes, void* stream);
+int gpk_nlml_grad_ragged(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_dev, int64_t hyp_stride,
+                         const double* noise_dev, int64_t noise_stride, const double* X, int64_t x_bstride,
+                         const double* y, int64_t y_bstride, const int64_t* n_dev, void* W, void* Winv,
+                         int32_t* info_dev, double* out_dev, double* grad_dev, void* work, size_t work_bytes,
+                         void* stream);
+
 /* Plain kernel matrix K[i*ldk + j] = k(X_i, Y_j) (+ diag_add where i == j) for i < n, j < m.
  * uplo: 0 = full, 1 = lower triangle only.  dtype selects the stored element type. */
 int gpk_kernel_matrix(const gpk_kdesc* kd, const double* hyp_dev, int dtype, int uplo,

@@ -23,7 +23,7 @@ LIB_PATH = os.path.join(HERE, LIB_NAME)
 SOURCES = ("gpk_assemble.hip", "gpk_grad.hip", "gpk_diag.hip", "gpk_potrf.hip", "gpk_approx.hip", "gpk_eig.hip",
            "gpk_flat.hip", "gpk_mean.hip", "gpk_fit.hip", "gpk_abi.hip",
            # host-only units: plain C++17 without a HIP header, built by the same hipcc line as the rest
-           "gpk_tune.cpp", "gpk_chain_plan.cpp")
+           "gpk_tune.cpp", "gpk_chain_plan.cpp", "gpk_launch_plan.cpp")
 ARCH = "gfx950"
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-Wno-unused-value"]
 

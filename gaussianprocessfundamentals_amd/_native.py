@@ -43,6 +43,7 @@ EXPORTS = (
     "gpk_op_supported", "gpk_mean_op_supported", "gpk_mean_eval", "gpk_mean_vjp_workspace_bytes", "gpk_mean_vjp",
     "gpk_fit_state_bytes", "gpk_fit_init", "gpk_fit_step", "gpk_fit_current",
     "gpk_assemble_inverse_ragged", "gpk_potrf_aug_ragged_ex", "gpk_grad_ragged", "gpk_nlml_grad_ragged",
+    "gpk_launch_plan",
 )
 # the ragged identity-augmented entries (added without a new ABI number, found by symbol)
 RAGGED_GRAD_ENTRIES = ("gpk_assemble_inverse_ragged", "gpk_potrf_aug_ragged_ex", "gpk_grad_ragged",
@@ -178,9 +179,11 @@ def _declare(lib):
                                     c_size_t, P]),
         "gpk_nlml_grad_ragged": (c_int, [POINTER(GpkKdesc), POINTER(GpkLayout), P, c_int64, P, c_int64, P, c_int64,
                                          P, c_int64, P, P, P, P, P, P, P, c_size_t, P]),
+        "gpk_launch_plan": (c_int, [POINTER(GpkLayout), c_int32, c_int32, c_int32, P, c_int64, POINTER(c_int64),
+                                    POINTER(c_int64)]),
     }
     for name, (res, args) in sig.items():
-        if (name == "gpk_op_supported" or name in RAGGED_GRAD_ENTRIES or
+        if (name in ("gpk_op_supported", "gpk_launch_plan") or name in RAGGED_GRAD_ENTRIES or
                 name.startswith(("gpk_mean_", "gpk_fit_"))) and not hasattr(lib, name):
             continue  # (a library built before the entry existed: *op_supported() / fit_supported() then say no)
         fn = getattr(lib, name)
@@ -366,6 +369,33 @@ def chain_plan(n_pad: int, y_row: int, grid: int, eye: bool = False, f32: bool =
     check(L.gpk_chain_plan_ex(int(n_pad), int(y_row), int(grid), fl, c_void_p(out.ctypes.data), int(nt.value),
                               ctypes.byref(nt)), "gpk_chain_plan_ex")
     return out
+
+
+# One step of gpk_launch_plan (include/gpk.h: GPK_LAUNCH_STEP_WORDS 8-byte words, in this order)
+LAUNCH_STEP_WORDS = 23
+LAUNCH_KINDS = ("diag", "trsm", "update", "record", "wait")
+LAUNCH_STREAMS = ("caller", "panel", "bulk")
+LAUNCH_EVENTS = ("fork", "panel", "bulk", "join_p", "join_b")
+LAUNCH_ROLES = ("", "thin", "half", "look-ahead", "bulk", "group")
+LAUNCH_STEP_FIELDS = ("kind", "stream", "event", "role", "cls", "kblk", "trsm_tiles", "j0", "row0", "kdepth", "tile",
+                      "nt", "c_lo", "c_hi", "zlo", "zhi", "bz0", "bzn", "band", "row_end", "kbuild")
+
+
+def launch_plan(lay: GpkLayout, eye: bool = False, counters: bool = True, kbuild: bool = False, first_group=False):
+    """The launch path's schedule for ``lay`` under the calling thread's knobs (gpk_launch_plan; host only): a
+    structured array, one record per launch or event edge in issue order -- the int64 fields LAUNCH_STEP_FIELDS, then
+    the float64 ``flops`` and ``bytes``.  first_group: return (steps, panels of the first group)."""
+    import numpy as np
+    L = load_library()
+    dt = np.dtype([(f, "<i8") for f in LAUNCH_STEP_FIELDS] + [("flops", "<f8"), ("bytes", "<f8")])
+    assert dt.itemsize == 8 * LAUNCH_STEP_WORDS
+    ns, g0 = c_int64(0), c_int64(0)
+    args = (ctypes.byref(lay), AUG_EXTRA_IDENTITY if eye else 0, int(bool(counters)), int(bool(kbuild)))
+    check(L.gpk_launch_plan(*args, None, 0, ctypes.byref(ns), ctypes.byref(g0)), "gpk_launch_plan")
+    out = np.zeros(int(ns.value), dtype=dt)
+    check(L.gpk_launch_plan(*args, c_void_p(out.ctypes.data), int(ns.value), ctypes.byref(ns), None),
+          "gpk_launch_plan")
+    return (out, int(g0.value)) if first_group else out
 
 
 def timing_reset():

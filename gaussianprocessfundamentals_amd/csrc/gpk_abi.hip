@@ -15,6 +15,7 @@
 #include "gpk_chain_plan.h"
 #include "gpk_internal.h"
 #include "gpk_kernels.h"
+#include "gpk_launch_plan.h"
 #include "gpk_tune.h"
 
 #ifndef GPK_DIAG_PROF
@@ -222,13 +223,12 @@ SideStream* side_stream() {
   return &ss;
 }
 
-// Ticket counters of the fused panel solve (DiagArgs::ctr), one block of kFuseCtr per (device,
+// Ticket counters of the fused panel solve (DiagArgs::ctr), one block of kFuseCtr (gpk_launch_plan.h) per (device,
 // stream): launches on one stream never overlap.  Tickets are drawn with atomicInc(ctr, grid - 1), so
 // the grid's last draw wraps the counter back to 0 by itself (no reset store).  A handle that stands
 // for one stream per host thread (hipStreamPerThread) or a stream being captured does not get
 // counters: its panel solve stays a separate launch (fuse_counters returns nullptr).  The null stream
 // is one queue per device whatever thread launches on it (torch's default stream), so it keeps them.
-constexpr int kFuseCtr = 256;  // members per launch
 std::mutex g_ctr_mu;
 std::map<std::pair<int, hipStream_t>, int32_t*> g_ctr;
 
@@ -625,7 +625,6 @@ static int potrf_impl(const gpk_layout* lay, void* W, void* Winv, int32_t* info_
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int dt = lay->dtype;
   const size_t es = elem_size(dt);
-  const int64_t nblk = lay->n_pad / NB;
 
   // one snapshot of the knobs per call: a gpk_tune from another thread (ctypes releases the GIL during
   // the enqueue) must not change the fuse decision between a panel's diag(k) and trsm(k)
@@ -637,77 +636,35 @@ static int potrf_impl(const gpk_layout* lay, void* W, void* Winv, int32_t* info_
     if (!e) note_factorisation(s);
     return e;
   }
-  // The panel chain (diag, panel solve, thin and look-ahead updates) runs on a high-priority
-  // stream, the bulk of each trailing update on a CU-masked stream concurrently with the next
-  // panel pair's chain; both fork from and join back into the caller's stream.
-  // GPK_LOOKAHEAD=0 puts everything on the caller's stream.
-  // Auto (2): on when the augmented matrix has at least la_min_blocks 128-blocks.  Below that the
-  // whole factorisation is faster on the caller's stream alone: each launch on the side streams costs
-  // ~5 us more than back to back on one queue, more than the overlap of the short trailing updates
-  // saves.  ms per call, look-ahead off / on (profiles/r02s_lookahead.txt): one member N = 1024
-  // 0.45 / 0.55, 2048 0.92 / 1.09, 4096 2.10 / 2.29, 6144 3.98 / 4.03, 8192 6.53 / 6.40, 12288
-  // 15.3 / 14.5; batches of 8 at N = 4096 5.13 / 5.26; the 128-candidate C4 sweep 52.7 / 54.2;
-  // -LML + gradient (identity rows: twice the width) N = 4096 3.44 / 3.28.  With the panel solve fused
-  // (look-ahead off only): N = 6144 3.89 / 4.02, 7168 5.01 / 5.05, 8192 6.43 / 6.39 -> 64 blocks.
-  const bool la = tn.lookahead == 1 || (tn.lookahead == 2 && lay->p / NB >= tn.la_min_blocks);
-  SideStream* ss = nullptr;
+  // Checks, plan, issue: the schedule -- which launches, on which logical stream, between which event edges, with
+  // what geometry and accounting -- is launch_plan's (gpk_launch_plan.cpp); here it meets the call's pointers,
+  // strides and queues.
+  const bool la = launch_lookahead(tn, lay->p);
+  static const SideStream no_side;  // look-ahead off: no event step, every step on the caller's stream
+  const SideStream* ss = &no_side;
   if (la) {
     ss = side_stream();
     if (!ss) return fail_hip(hipErrorInvalidValue, "side stream");
   }
   hipStream_t sp = !la ? s : tn.panel_stream == 1 ? s : tn.panel_stream == 2 ? ss->panel_np : ss->panel_s;
-  hipStream_t sb = la ? ss->bulk_s : s;
-
-  // extra rows that are nonzero in panel columns left of c: all test rows, or the identity rows
-  // t < c (row n_pad + t of E L^-T is zero left of column t)
-  auto extra_nonzero = [&](int64_t c) -> double {
-    return (double)(eye ? std::min<int64_t>(lay->m, c) : lay->m);
-  };
-  // Small grids (f64): the panel solve of block k runs inside the diagonal-block launch -- one
-  // workgroup per 64-row tile (plus the one that writes L and L^-1), each factoring the block
-  // redundantly (the chip is otherwise idle there) and solving its rows against L^-1 in LDS, bitwise
-  // the separate gemm<TRSM>; one launch fewer on the chain per panel.
+  const hipStream_t queue[3] = {s, sp, la ? ss->bulk_s : s};                                     // by LP_CALLER ..
+  const hipEvent_t event[LP_NUM_EVENTS] = {ss->fork, ss->panel, ss->bulk, ss->join_p, ss->join_b};  // by LP_EV_*
   int32_t* const ctr = (dt == GPK_F64 && tn.fuse_trsm) ? fuse_counters(sp) : nullptr;
-  auto fused_tiles = [&](int64_t k) -> int64_t {
-    const int64_t rows = lay->p - (k + 1) * NB;
-    if (!ctr) return 0;  // no counters for this stream: the separate panel-solve launch
-    // (the timing-only ablations of the diagonal kernel skip the writer's counter reset: never fused)
-    if (dt != GPK_F64 || !tn.fuse_trsm || tn.diag_version == 1 || tn.diag_dbg != 0 || rows <= 0) return 0;
-    if (la && tn.fuse_trsm != 2) return 0;  // beside the look-ahead's bulk updates the extra workgroups
-                                             // cost more than the launch saves (N = 8192: 6.39 -> 6.43 ms)
-    const int64_t t64 = rows / 64;
-    return (t64 + 1) * lay->batch <= tn.fuse_trsm_max && lay->batch <= kFuseCtr ? t64 : 0;
-  };
-  // diagonal block k: factor + invert
-  auto diag = [&](int64_t k) -> hipError_t {
-    DiagArgs da;
-    memset(&da, 0, sizeof(da));
-    da.W = W;
-    da.ld = lay->ld;
-    da.w_bs = lay->w_batch_stride;
-    da.Winv = Winv;
-    da.inv_bs = lay->inv_batch_stride;
-    da.j0 = k * NB;
-    da.kblk = k;
-    da.info = info_dev;
-    da.dbg = (int32_t)tn.diag_dbg;
-    da.version = (int32_t)tn.diag_version;
-    da.trsm_tiles = (int32_t)fused_tiles(k);
-    double flops = (double)lay->batch * NB * NB * NB / 3.0;
-    if (da.trsm_tiles > 0) {
-      da.row0 = (k + 1) * NB;
-      da.p = lay->p;
-      da.n_pad = lay->n_pad;
-      da.y_row = lay->y_row;
-      da.zlo = eye ? lay->n_pad + da.row0 : 0;  // identity rows t >= j0 + nb are still zero
-      da.zhi = eye ? lay->y_row : 0;
-      da.nb = n_dev;
-      da.mb = m_dev;
-      da.ctr = ctr;
-      flops += (double)lay->batch * ((double)(lay->n_pad - da.row0) + extra_nonzero(da.row0)) * NB * NB;
-    }
-    return timed(1, flops, 0.0, sp, [&] { return launch_diag(da, dt, lay->batch, sp); });
-  };
+
+  thread_local std::vector<LaunchStep> steps;  // (reused: no allocation per call once it has grown)
+  launch_plan({dt == GPK_F32, lay->batch, lay->m, lay->n_pad, lay->y_row, lay->p}, eye, ctr != nullptr, kb != nullptr,
+              tn, steps);
+
+  DiagArgs dbase;
+  memset(&dbase, 0, sizeof(dbase));
+  dbase.W = W;
+  dbase.ld = lay->ld;
+  dbase.w_bs = lay->w_batch_stride;
+  dbase.Winv = Winv;
+  dbase.inv_bs = lay->inv_batch_stride;
+  dbase.info = info_dev;
+  dbase.dbg = (int32_t)tn.diag_dbg;
+  dbase.version = (int32_t)tn.diag_version;
   GemmArgs base;
   memset(&base, 0, sizeof(base));
   base.W = W;
@@ -719,164 +676,65 @@ static int potrf_impl(const gpk_layout* lay, void* W, void* Winv, int32_t* info_
   base.n_pad = lay->n_pad;
   base.y_row = lay->y_row;
   base.p = lay->p;
-  base.row_end = tn.skip_zero_rows ? lay->y_row + 1 : 0;  // rows below the y row are zero
-  // identity extra rows: the tiles wholly inside the zero band [zlo, zhi) are left out of the grid
-  // (launched and exiting at once they would also crowd the live tiles onto a few XCDs, since
-  // xcd_remap hands each XCD a contiguous run of tile ids).  c: a tile index from row0 -> its index
-  // in the compressed enumeration.
-  auto set_band = [&](GemmArgs& ga, int tile) {
-    if (!eye || !tn.band_skip) return;
-    const int64_t b0 = (ga.zlo - ga.row0) / tile, b1 = (ga.zhi - ga.row0) / tile;
-    if (b1 <= b0) return;
-    ga.bz0 = (int32_t)b0;
-    ga.bzn = (int32_t)(b1 - b0);
-  };
-  auto compress = [](const GemmArgs& ga, int64_t c) -> int64_t {
-    return ga.bzn == 0 || c < ga.bz0 ? c : (c >= (int64_t)ga.bz0 + ga.bzn ? c - ga.bzn : ga.bz0);
-  };
-  // panel solve of block k: every row below the block (the y / test rows included)
-  auto trsm = [&](int64_t k) -> hipError_t {
-    if (fused_tiles(k) > 0) return hipSuccess;  // solved by the diagonal-block launch
-    GemmArgs ga = base;
-    ga.Binv = static_cast<const char*>(Winv) + (size_t)k * NB * NB * es;
-    ga.j0 = k * NB;
-    ga.row0 = ga.j0 + NB;
-    const int64_t rows = lay->p - ga.row0;
-    if (rows <= 0) return hipSuccess;
-    ga.kdepth = NB;
-    if (eye) {  // identity rows t >= j0 + nb are still zero in this panel
-      ga.zlo = lay->n_pad + ga.j0 + NB;
-      ga.zhi = lay->y_row;
+  static const char* const update_label[] = {"update", "update thin", "update half", "update look-ahead",
+                                             "update bulk", "update"};  // by LP_ROLE_*
+  for (const LaunchStep& st : steps) {
+    const hipStream_t q = queue[st.stream];
+    if (st.kind == LP_RECORD) {
+      GPK_HIP(hipEventRecord(event[st.event], q), "event");
+    } else if (st.kind == LP_WAIT) {
+      GPK_HIP(hipStreamWaitEvent(q, event[st.event], 0), "event");
+    } else if (st.kind == LP_DIAG) {
+      DiagArgs da = dbase;
+      da.j0 = st.j0;
+      da.kblk = st.kblk;
+      da.trsm_tiles = (int32_t)st.trsm_tiles;
+      if (da.trsm_tiles > 0) {  // the panel solve inside the launch
+        da.row0 = st.row0;
+        da.p = lay->p;
+        da.n_pad = lay->n_pad;
+        da.y_row = lay->y_row;
+        da.zlo = st.zlo;
+        da.zhi = st.zhi;
+        da.nb = n_dev;
+        da.mb = m_dev;
+        da.ctr = ctr;
+      }
+      GPK_HIP(timed((int)st.cls, st.flops, st.bytes, q, [&] { return launch_diag(da, dt, lay->batch, q); }), "diag");
+    } else {
+      GemmArgs ga = base;
+      ga.j0 = st.j0;
+      ga.row0 = st.row0;
+      ga.kdepth = (int32_t)st.kdepth;
+      ga.nt = (int32_t)st.nt;
+      ga.c_lo = (int32_t)st.c_lo;
+      ga.c_hi = (int32_t)st.c_hi;
+      ga.zlo = st.zlo;
+      ga.zhi = st.zhi;
+      ga.bz0 = (int32_t)st.bz0;
+      ga.bzn = (int32_t)st.bzn;
+      ga.band = (int32_t)st.band;
+      ga.row_end = st.row_end;
+      const bool solve = st.kind == LP_TRSM;
+      if (solve) ga.Binv = static_cast<const char*>(Winv) + (size_t)(st.j0 / NB) * NB * NB * es;
+      if (st.kbuild) {  // C is evaluated, not loaded (gpk_nlml's fused K build)
+        ga.kbuild = 1;
+        ga.d = kb->d;
+        ga.n = kb->n;
+        ga.node = kb->node;
+        ga.hyp = kb->hyp;
+        ga.hyp_stride = kb->hyp_stride;
+        ga.noise = kb->noise;
+        ga.noise_stride = kb->noise_stride;
+        ga.X = kb->X;
+        ga.x_bs = kb->x_bs;
+        ga.y = kb->y;
+        ga.y_bs = kb->y_bs;
+      }
+      GPK_HIP(timed((int)st.cls, st.flops, st.bytes, q,
+                    [&] { return launch_gemm(ga, dt, solve ? GEMM_TRSM : GEMM_UPDATE, (int)st.tile, lay->batch, q); }),
+              solve ? "trsm" : update_label[st.role]);
     }
-    set_band(ga, 128);
-    const int tile = (compress(ga, rows / NB) * lay->batch >= tn.trsm_t128_min) ? 128 : 64;
-    ga.bz0 = ga.bzn = 0;
-    set_band(ga, tile);
-    ga.nt = (int32_t)compress(ga, rows / tile);
-    // algorithmic: rows that are nonzero in the panel (K part + extra rows) x nb^2
-    const double rK = (double)(lay->n_pad - ga.row0) + extra_nonzero(ga.j0 + NB);
-    return timed(2, (double)lay->batch * rK * NB * NB, 0.0, sp,
-                 [&] { return launch_gemm(ga, dt, GEMM_TRSM, tile, lay->batch, sp); });
-  };
-  // trailing update from panel columns [j0, j0 + kdepth) of the lower tiles whose 128-column
-  // block lies in [c_lo, c_hi) (relative to row0 = j0 + kdepth; c_hi < 0: to the end)
-  auto update = [&](int64_t j0, int kdepth, int64_t c_lo, int64_t c_hi, hipStream_t st,
-                    bool fused_k = false) -> hipError_t {
-    GemmArgs ga = base;
-    if (fused_k && kb) {  // first trailing update: C is evaluated, not loaded (gpk_nlml's fused K build)
-      ga.kbuild = 1;
-      ga.d = kb->d;
-      ga.n = kb->n;
-      ga.node = kb->node;
-      ga.hyp = kb->hyp;
-      ga.hyp_stride = kb->hyp_stride;
-      ga.noise = kb->noise;
-      ga.noise_stride = kb->noise_stride;
-      ga.X = kb->X;
-      ga.x_bs = kb->x_bs;
-      ga.y = kb->y;
-      ga.y_bs = kb->y_bs;
-    }
-    ga.j0 = j0;
-    ga.row0 = j0 + kdepth;
-    ga.kdepth = kdepth;
-    const int64_t rows = lay->p - ga.row0;
-    if (rows <= 0) return hipSuccess;
-    const int64_t t128 = rows / NB;
-    if (c_hi < 0 || c_hi > t128) c_hi = t128;
-    if (c_lo >= c_hi) return hipSuccess;
-    if (eye) {  // identity rows t >= j0 + kdepth are zero in the panel columns
-      ga.zlo = lay->n_pad + j0 + kdepth;
-      ga.zhi = lay->y_row;
-    }
-    set_band(ga, 128);
-    const int64_t w128 = compress(ga, c_hi) - compress(ga, c_lo);
-    if (w128 <= 0) return hipSuccess;
-    const int64_t tiles128 = w128 * (w128 + 1) / 2 + (compress(ga, t128) - compress(ga, c_hi)) * w128;
-    const int tile = (tiles128 * lay->batch >= tn.upd_t128_min) ? 128 : 64;
-    const int64_t scale = NB / tile;
-    ga.bz0 = ga.bzn = 0;
-    set_band(ga, tile);
-    ga.nt = (int32_t)compress(ga, rows / tile);
-    ga.c_lo = (int32_t)compress(ga, c_lo * scale);
-    ga.c_hi = (int32_t)compress(ga, c_hi * scale);
-    ga.band = (int32_t)std::max<int64_t>(0, tn.upd_band);
-    // algorithmic flops: 2 kdepth x (lower-triangle elements in the column range of the rows that
-    // are nonzero in the panel: the K part, then the extra rows, which follow it contiguously)
-    const double rK = (double)(lay->n_pad - ga.row0) + extra_nonzero(j0 + kdepth);
-    const double cl = std::min(rK, (double)(c_lo * NB)), ch = std::min(rK, (double)(c_hi * NB));
-    const double elems = (ch - cl) * rK - (cl + ch - 1.0) * (ch - cl) / 2.0;
-    // algorithmic bytes: the updated tiles' elements read + written once (y / test rows too)
-    // and the panel rows read once
-    const double rA = (double)rows;
-    const double ca = (double)(c_lo * NB), cb = (double)(c_hi * NB);
-    const double elems_all = (cb - ca) * rA - (ca + cb - 1.0) * (cb - ca) / 2.0;
-    const double bytes = (double)lay->batch * (double)es * (2.0 * elems_all + rA * kdepth);
-    return timed(3, (double)lay->batch * 2.0 * kdepth * std::max(0.0, elems), bytes, st,
-                 [&] { return launch_gemm(ga, dt, GEMM_UPDATE, tile, lay->batch, st); });
-  };
-
-  // Groups of G 128-column panels per trailing update (K = 128 G): inside the group, block column k
-  // is brought up to date with the group's earlier panels (one left-looking update of depth
-  // 128 (k - g0)) and then factored and solved, ..., then update the trailing
-  // matrix with all G panels at once -- its first G block columns (look-ahead, on the panel
-  // stream: the next group's panels) and the rest (bulk stream, overlapping the next group's
-  // panel chain).  A deeper K halves the read-modify-write passes over the trailing matrix per
-  // doubling of G.  The first group has G0 <= G panels: its chain is exposed (nothing to overlap
-  // yet), so a short one lets the first bulk update start early.
-  // identity-augmented (gradient / inverse) factorisations: groups of group_eye panels -- their
-  // trailing matrix carries the K^-1 corner, and 4-panel groups measured faster there at every batch
-  const int64_t G = std::max<int64_t>(1, std::min<int64_t>(eye ? tn.group_eye : tn.group, 16));
-  const int64_t G0 = std::max<int64_t>(1, std::min<int64_t>(tn.group_first, G));
-  if (la) {
-    GPK_HIP(hipEventRecord(ss->fork, s), "event");
-    GPK_HIP(hipStreamWaitEvent(sp, ss->fork, 0), "event");
-    GPK_HIP(hipStreamWaitEvent(sb, ss->fork, 0), "event");
-  }
-  // In-group updates.  Left-looking (throughput): block column k receives the group's earlier
-  // panels in ONE update of depth 128 (k - g0) right before its diagonal block is factored
-  // (right-looking updates read and write the group's columns once per panel).  Right-looking
-  // (latency, small batches whose thin launches cannot fill the chip): after panel k, the group's
-  // remaining columns receive panel k at depth 128 -- the chain to diag(k + 1) then carries one
-  // short update instead of one of depth up to 128 (G - 1).
-  // Two-level left-looking (ingroup 3): the group is split in halves; each half is left-looking
-  // within itself, and between the halves ONE update of the second half's columns with the first
-  // half's panels (depth 128 G/2) -- the thin launches re-read the half's panels instead of the
-  // group's, 36 instead of 42 panel-column reads + writes per group of 8 (they are HBM-bound).
-  const int64_t rows128 = lay->p / NB;
-  const bool right_looking = tn.ingroup == 2 || (tn.ingroup == 0 && lay->batch * rows128 < tn.rl_max_tiles);
-  const bool two_level = !right_looking && (tn.ingroup == 3 || tn.ingroup == 0) && G >= 4;
-  bool bulk_pending = false;
-  for (int64_t g0 = 0, gsize = G0; g0 < nblk; g0 += gsize, gsize = G) {
-    const int64_t gend = std::min(g0 + gsize, nblk);
-    const int64_t gmid = two_level ? std::min(g0 + (gend - g0 + 1) / 2, gend) : gend;
-    for (int64_t k = g0; k < gend; ++k) {
-      const int64_t h0 = k < gmid ? g0 : gmid;  // first panel of k's half
-      if (two_level && k == gmid && gmid > g0)
-        GPK_HIP(update(g0 * NB, (int)((gmid - g0) * NB), 0, gend - gmid, sp), "update half");
-      if (!right_looking && k > h0) GPK_HIP(update(h0 * NB, (int)((k - h0) * NB), 0, 1, sp), "update thin");
-      GPK_HIP(diag(k), "diag");
-      GPK_HIP(trsm(k), "trsm");
-      if (right_looking && k + 1 < gend) GPK_HIP(update(k * NB, NB, 0, gend - k - 1, sp), "update thin");
-    }
-    const int kd = (int)((gend - g0) * NB);
-    if (!la) {
-      GPK_HIP(update(g0 * NB, kd, 0, -1, s, g0 == 0), "update");
-      continue;
-    }
-    GPK_HIP(hipEventRecord(ss->panel, sp), "event");      // panels g0 .. gend-1 solved
-    if (bulk_pending) GPK_HIP(hipStreamWaitEvent(sp, ss->bulk, 0), "event");
-    GPK_HIP(update(g0 * NB, kd, 0, G, sp, g0 == 0), "update look-ahead");
-    GPK_HIP(hipStreamWaitEvent(sb, ss->panel, 0), "event");
-    GPK_HIP(update(g0 * NB, kd, G, -1, sb, g0 == 0), "update bulk");
-    GPK_HIP(hipEventRecord(ss->bulk, sb), "event");
-    bulk_pending = true;
-  }
-  if (la) {
-    GPK_HIP(hipEventRecord(ss->join_p, sp), "event");
-    GPK_HIP(hipEventRecord(ss->join_b, sb), "event");
-    GPK_HIP(hipStreamWaitEvent(s, ss->join_p, 0), "event");
-    GPK_HIP(hipStreamWaitEvent(s, ss->join_b, 0), "event");
   }
   note_factorisation(s);
   return 0;
@@ -966,11 +824,9 @@ int gpk_nlml(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_dev, 
   // assembled; the first trailing update evaluates its C tiles instead of reading them, so the
   // trailing part of K is never written to HBM and read back.
   const Tune tn = tune_now();
-  const int64_t nblk = lay->n_pad / NB;
-  const int64_t G = std::max<int64_t>(1, std::min<int64_t>(tn.group, 16));
-  const int64_t G0 = std::max<int64_t>(1, std::min<int64_t>(tn.group_first, G));
+  const int64_t G0 = launch_first_group(tn, false, lay->n_pad);  // (a single group has no trailing matrix to build)
   const int op0 = kd ? kd->nodes[0].op : 0;
-  if (tn.fuse_kbuild && lay->dtype == GPK_F64 && valid_kdesc(kd, lay->d) && kd->n_nodes == 1 && G0 < nblk &&
+  if (tn.fuse_kbuild && lay->dtype == GPK_F64 && valid_kdesc(kd, lay->d) && kd->n_nodes == 1 && G0 < lay->n_pad / NB &&
       !chain_applies(lay, false, nullptr, nullptr, tn, s) &&
       (op0 == GPK_OP_SE || op0 == GPK_OP_MAT32 || op0 == GPK_OP_MAT52)) {
     int e = assemble_impl(kd, lay, hyp_dev, hyp_stride, noise_dev, noise_stride, X, x_bstride, nullptr, 0,
@@ -1998,6 +1854,27 @@ int gpk_chain_plan(int64_t n_pad, int64_t y_row, int32_t grid, int32_t* tasks_ou
 int gpk_chain_plan_ex(int64_t n_pad, int64_t y_row, int32_t grid, int32_t flags, int32_t* tasks_out, int64_t cap,
                       int64_t* ntasks) {
   return chain_plan_impl(n_pad, y_row, grid, flags, tasks_out, cap, ntasks, 6, 7);
+}
+
+int gpk_launch_plan(const gpk_layout* lay, int32_t flags, int32_t counters, int32_t kbuild, void* steps_out, int64_t cap,
+                    int64_t* nsteps, int64_t* first_group) {
+  static_assert(GPK_LAUNCH_STEP_WORDS == kLaunchStepWords, "gpk.h documents LaunchStep word by word");
+  if (int e = check_layout(lay)) return e;
+  if (flags & ~GPK_AUG_EXTRA_IDENTITY) return fail_arg(2, "flags");
+  const bool eye = (flags & GPK_AUG_EXTRA_IDENTITY) != 0;
+  if (eye && lay->m != lay->n) return fail_arg(1, "identity extra rows need a layout planned with m = n");
+  if (!nsteps) return fail_arg(7, "nsteps");
+  const Tune tn = tune_now();
+  std::vector<LaunchStep> steps;
+  launch_plan({lay->dtype == GPK_F32, lay->batch, lay->m, lay->n_pad, lay->y_row, lay->p}, eye, counters != 0,
+              kbuild != 0, tn, steps);
+  *nsteps = (int64_t)steps.size();
+  if (first_group) *first_group = launch_first_group(tn, eye, lay->n_pad);
+  if (steps_out) {
+    if (cap < *nsteps) return fail_arg(6, "cap (fewer than nsteps)");
+    memcpy(steps_out, steps.data(), steps.size() * sizeof(LaunchStep));
+  }
+  return 0;
 }
 
 int gpk_tune(const char* key, int64_t value, int64_t* old) {

@@ -14,7 +14,7 @@
   KN(diag_dbg, 0, "diag_debug", "GPK_DIAG_DEBUG")                                                                      \
                            /* timing-only ablation flags of the diagonal kernel (never set in production) */           \
   K(lookahead, 2)          /* 1: panel chain on a high-priority side stream, 0: one stream, 2: auto (default:          \
-                              on for large matrices, see potrf_impl) */                                                \
+                              on for large matrices, launch_lookahead) */                                              \
   K(la_min_blocks, 64)     /* auto look-ahead: on from this many 128-blocks of the augmented matrix */                 \
   K(fuse_trsm, 1)          /* f64: panel solve fused into the diagonal-block launch (1: look-ahead off only,           \
                               2: always; one workgroup per */                                                          \

@@ -696,6 +696,28 @@ int gpk_chain_plan(int64_t n_pad, int64_t y_row, int32_t grid, int32_t* tasks_ou
 int gpk_chain_plan_ex(int64_t n_pad, int64_t y_row, int32_t grid, int32_t flags, int32_t* tasks_out, int64_t cap,
                       int64_t* ntasks);
 
+/* The schedule of the launch path (no reference counterpart -- it replaces nothing in gpbasics; introspection only):
+ * the launches and event edges gpk_potrf_aug / _ex / _ragged enqueue, in order, for this layout when the persistent
+ * launch does not apply (gpk_tune "chain"), under the knobs in effect for the calling thread.  flags: those of
+ * gpk_potrf_aug_ex.  counters: nonzero if the panel stream has the fused panel solve's ticket counters (every
+ * ordinary stream; not hipStreamPerThread or a stream being captured).  kbuild: nonzero for gpk_nlml's factorisation
+ * with the K build fused into the first trailing update.  One step is GPK_LAUNCH_STEP_WORDS 8-byte words, 21 int64
+ * and two doubles:
+ *   0 kind (0 diagonal block, 1 panel solve, 2 trailing update, 3 event record, 4 wait for event)
+ *   1 stream (0 the caller's, 1 panel, 2 bulk; with the look-ahead off every step is on 0)
+ *   2 event (record / wait: 0 fork, 1 panel, 2 bulk, 3 join_p, 4 join_b; else -1)
+ *   3 role of an update (1 thin, 2 half, 3 look-ahead, 4 bulk, 5 a group's whole trailing update; else 0)
+ *   4 timing class (gpk_timing_read; events -1)     5 kblk (diagonal block)
+ *   6 trsm_tiles (diagonal block: 64-row tiles of the panel solve fused into the launch; then no step of kind 1)
+ *   7 j0   8 row0   9 kdepth   10 tile edge   11 nt   12 c_lo   13 c_hi   14 zlo   15 zhi   16 bz0   17 bzn
+ *   18 band   19 row_end   20 kbuild (the launch arguments of the same names)
+ *   21 flops, 22 bytes (doubles: the algorithmic work gpk_timing_read accumulates for the launch).
+ * Host only (no device call): steps_out may be NULL to query *nsteps; cap = its capacity in steps.  *first_group
+ * (may be NULL): the panels of the first group -- the diagonal-block steps before the first step with kbuild set. */
+#define GPK_LAUNCH_STEP_WORDS 23
+int gpk_launch_plan(const gpk_layout* lay, int32_t flags, int32_t counters, int32_t kbuild, void* steps_out,
+                    int64_t cap, int64_t* nsteps, int64_t* first_group);
+
 #ifdef __cplusplus
 }
 #endif

@@ -71,6 +71,12 @@ def test_struct_sizes_match_header(lib):
     assert ctypes.sizeof(_native.GpkNode) == 16
     assert ctypes.sizeof(_native.GpkKdesc) == 16 + 16 * 16
     assert ctypes.sizeof(_native.GpkLayout) == 8 + 10 * 8 + 2 * 8
+    # one step of gpk_launch_plan: GPK_LAUNCH_STEP_WORDS 8-byte words, the int64 fields and the two doubles
+    words = int(re.search(r"#define GPK_LAUNCH_STEP_WORDS (\d+)", open(HEADER).read()).group(1))
+    assert words == _native.LAUNCH_STEP_WORDS == len(_native.LAUNCH_STEP_FIELDS) + 2
+    steps = _native.launch_plan(_native.plan(_native.GPK_F64, 1, 300, 77, 2))
+    assert steps.dtype.itemsize == 8 * words and steps.dtype.names[-2:] == ("flops", "bytes")
+    assert len(steps) > 0 and set(steps["kind"]) <= set(range(len(_native.LAUNCH_KINDS)))
 
 
 def test_product_fails_loudly_without_gpu(lib):

@@ -2,59 +2,47 @@
 (bulk, K = 128 G) launches and the in-group launches, with their achieved TF/s.
 
 usage: python tools/update_split.py bench_out/prof/run_kernel_trace.csv N BATCH [G] [INGROUP] [depth]
-INGROUP: 3 two-level left-looking (the default schedule for batches that fill the chip), 1 left-looking.
-Flops per launch: 2 K x (lower-triangle elements of the updated columns over the K rows), from the launch
-order of gpk_potrf_aug (gpk_abi.hip potrf_impl):
-  left-looking (1): per group, before panel k > g0 one update of block column k with panels g0 .. k-1;
-  two-level (3):    the group split at gmid = g0 + ceil(G / 2); each half left-looking within itself, and
-                    before panel gmid ONE update of columns gmid .. gend-1 with panels g0 .. gmid-1 ("half");
-then the group update of the trailing matrix with all G panels.  "depth" adds a per-depth table.
+G / INGROUP: gpk_tune "group" / "ingroup" of the traced run (default: the library's, environment included).
+The sequence of update launches, their depths and their flops are the library's own schedule for the shape
+(nat.launch_plan with the look-ahead off), so every in-group mode and the fused K build are covered; the steps are
+labelled by their role: thin, half, or group (a group's trailing update).  "depth" adds a per-depth table.
 """
 import csv
+import os
 import sys
 
-
-def elems(n, row0, w):
-    """lower-triangle elements of block columns [row0, row0 + 128 w) over rows [row0, n)"""
-    ra, cb = n - row0, min(128 * w, n - row0)
-    return cb * ra - (cb - 1.0) * cb / 2.0
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from gaussianprocessfundamentals_amd import _native as nat  # noqa: E402
 
 
-def model(n, G, ingroup):
-    nb = n // 128
-    seq = []
-    for g0 in range(0, nb, G):
-        gend = min(g0 + G, nb)
-        gmid = min(g0 + (gend - g0 + 1) // 2, gend) if ingroup == 3 else gend
-        for k in range(g0, gend):
-            h0 = g0 if k < gmid else gmid
-            if ingroup == 3 and k == gmid and gmid > g0:
-                d = gmid - g0
-                seq.append(("half", 128 * d, 2.0 * 128 * d * elems(n, 128 * gmid, gend - gmid)))
-            if k > h0:
-                d = k - h0
-                seq.append(("thin", 128 * d, 2.0 * 128 * d * elems(n, 128 * k, 1)))
-        rows = n - 128 * gend
-        seq.append(("group", 128 * (gend - g0), 2.0 * 128 * (gend - g0) * rows * (rows + 1) / 2))
-    return seq
+def sequence(n, batch, knobs):
+    """(label, depth, flops of the whole batch) of every update launch, in issue order"""
+    lay = nat.plan(nat.GPK_F64, batch, n, 0, 1)
+    with nat.thread_tune(lookahead=0, **knobs):
+        steps = nat.launch_plan(lay)
+    label = {"thin": "thin", "half": "half"}
+    return [(label.get(nat.LAUNCH_ROLES[int(s["role"])], "group"), int(s["kdepth"]), float(s["flops"]))
+            for s in steps if nat.LAUNCH_KINDS[int(s["kind"])] == "update"]
 
 
 def main():
     path, n, batch = sys.argv[1], int(sys.argv[2]), int(sys.argv[3])
-    G = int(sys.argv[4]) if len(sys.argv) > 4 else 8
-    ingroup = int(sys.argv[5]) if len(sys.argv) > 5 else 3
+    knobs = {}
+    if len(sys.argv) > 4:
+        knobs["group"] = int(sys.argv[4])
+    if len(sys.argv) > 5:
+        knobs["ingroup"] = int(sys.argv[5])
     rows = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"])
                   for r in csv.DictReader(open(path)))
     starts = [i for i, r in enumerate(rows) if "assemble_kernel" in r[2]]
     step = rows[starts[-1]:]
     upd = [(s, e) for s, e, k in step if "gemm_kernel<double, 0" in k or "gemm_kernel<float, 0" in k]
-    seq = model(n, G, ingroup)
+    seq = sequence(n, batch, knobs)
     if len(seq) != len(upd):
-        print("launch count mismatch: trace %d, model %d" % (len(upd), len(seq)))
+        print("launch count mismatch: trace %d, plan %d (other knobs than the traced run's?)" % (len(upd), len(seq)))
     tot = {}
     bydepth = {}
     for (s, e), (kind, depth, fl) in zip(upd, seq):
-        fl *= batch
         t = tot.setdefault(kind, [0.0, 0.0, 0])
         t[0] += (e - s) * 1e-9
         t[1] += fl
@@ -66,7 +54,7 @@ def main():
             b[2] += 1
     for kind, (sec, fl, cnt) in tot.items():
         print("%-5s %3d launches  %.3f ms  %.1f TF/s" % (kind, cnt, sec * 1e3, fl / max(sec, 1e-12) / 1e12))
-    big = [(e - s, fl * batch) for (s, e), (kind, _, fl) in zip(upd, seq) if kind == "group"]
+    big = [(e - s, fl) for (s, e), (kind, _, fl) in zip(upd, seq) if kind == "group"]
     for dt, fl in big[:4] + big[-3:]:
         print("   group launch %.1f us  %.1f TF/s" % (dt / 1e3, fl / max(dt * 1e-9, 1e-12) / 1e12))
     if "depth" in sys.argv[6:]:

@@ -137,7 +137,9 @@ class DeviceLbfgsFitter(GradientFitter):
         self.steps = 0
         self.status_reads = 0
 
-    # -- what the class accepts (the k-fold sibling overrides the data-input part) ------------------
+    # -- what the class accepts (the k-fold sibling overrides the data-input part, the MSE siblings the metric) ----
+    _METRICS = (met.MetricType.LL, met.MetricType.BIC)
+
     @classmethod
     def _check_data_input(cls, data_input):
         name = cls.__name__
@@ -153,8 +155,9 @@ class DeviceLbfgsFitter(GradientFitter):
     def _check_supported(cls, data_input, gaussian_process, metric_type, local_approx, numerical_matrix_handling):
         name = cls.__name__
         inputs = cls._check_data_input(data_input)
-        if metric_type not in (met.MetricType.LL, met.MetricType.BIC):
-            raise NotImplementedError("%s: metric %s is not supported (LL, BIC)" % (name, metric_type.name))
+        if metric_type not in cls._METRICS:
+            raise NotImplementedError("%s: metric %s is not supported (%s)"
+                                      % (name, metric_type.name, ", ".join(t.name for t in cls._METRICS)))
         if local_approx is not mht.MatrixApproximations.NONE:
             raise NotImplementedError("%s: approximation %s is not supported" % (name, local_approx.name))
         if numerical_matrix_handling is not mht.NumericalMatrixHandlingType.CHOLESKY_BASED:
@@ -298,3 +301,54 @@ class DeviceKfoldLbfgsFitter(DeviceLbfgsFitter):
     def _metric_value(self, hyper_parameter, noise):
         values = [m.get_metric(hyper_parameter, noise).reshape(1, 1) for m in self.metric]
         return torch.mean(torch.stack(values), dim=0)
+
+
+def _check_has_test_points(name: str, data_input) -> None:
+    x_test = getattr(data_input, "data_x_test", None)
+    if x_test is None or int(x_test.shape[0]) < 1:
+        raise NotImplementedError("%s: a data input without test points is not supported (the MSE is measured on "
+                                  "them)" % name)
+
+
+class DeviceMseLbfgsFitter(DeviceLbfgsFitter):
+    """:class:`DeviceLbfgsFitter` for the exact, Cholesky-based held-out MSE of a DataInput with test data: the loop,
+    starts, bounds and report are the sibling's; every iteration's evaluation is ONE batched factorisation with the
+    test points as extra rows plus the MSE gradient pass (sweep.native_batched_mse_value_and_gradient ->
+    gpk_mse_grad).  Pre- and post-fit metrics are MeanSquaredError.get_metric.  With a scaled kernel and an optimised
+    noise the MSE is invariant along (sg, noise) -> (c sg, c noise): the minimiser is a ray, compare objective values."""
+
+    _METRICS = (met.MetricType.MSE,)
+
+    @classmethod
+    def _check_data_input(cls, data_input):
+        inputs = super()._check_data_input(data_input)
+        _check_has_test_points(cls.__name__, inputs[0])
+        return inputs
+
+    def _evaluator(self, kernel):
+        from .. import sweep
+        di = self.data_input
+        return sweep.native_batched_mse_value_and_gradient(kernel, di.data_x_train, di.get_detrended_y_train(),
+                                                           di.data_x_test, di.get_detrended_y_test())
+
+
+class DeviceKfoldMseLbfgsFitter(DeviceKfoldLbfgsFitter):
+    """:class:`DeviceKfoldLbfgsFitter` for the mean of the folds' held-out MSE -- what CrossValidation(metric_type=MSE)
+    evaluates -- for every start and fold as ONE ragged batch per iteration
+    (sweep.native_kfold_mse_value_and_gradient -> gpk_mse_grad with n_dev / m_dev).  ``data_input`` is the list of
+    folds, e.g. CrossValidation.get_data_inputs; every fold needs test points."""
+
+    _METRICS = (met.MetricType.MSE,)
+
+    @classmethod
+    def _check_data_input(cls, data_input):
+        folds = super()._check_data_input(data_input)
+        for fold in folds:
+            _check_has_test_points(cls.__name__, fold)
+        return folds
+
+    def _evaluator(self, kernel):
+        from .. import sweep
+        return sweep.native_kfold_mse_value_and_gradient(
+            kernel, [(di.data_x_train, di.get_detrended_y_train(), di.data_x_test, di.get_detrended_y_test())
+                     for di in self.data_input])

@@ -43,11 +43,13 @@ EXPORTS = (
     "gpk_op_supported", "gpk_mean_op_supported", "gpk_mean_eval", "gpk_mean_vjp_workspace_bytes", "gpk_mean_vjp",
     "gpk_fit_state_bytes", "gpk_fit_init", "gpk_fit_step", "gpk_fit_current",
     "gpk_assemble_inverse_ragged", "gpk_potrf_aug_ragged_ex", "gpk_grad_ragged", "gpk_nlml_grad_ragged",
-    "gpk_launch_plan",
+    "gpk_launch_plan", "gpk_mse_grad_workspace_bytes", "gpk_mse_backward", "gpk_mse_grad",
 )
 # the ragged identity-augmented entries (added without a new ABI number, found by symbol)
 RAGGED_GRAD_ENTRIES = ("gpk_assemble_inverse_ragged", "gpk_potrf_aug_ragged_ex", "gpk_grad_ragged",
                        "gpk_nlml_grad_ragged")
+# the held-out MSE and its gradient (likewise)
+MSE_GRAD_ENTRIES = ("gpk_mse_grad_workspace_bytes", "gpk_mse_backward", "gpk_mse_grad")
 
 
 class NativeUnavailable(RuntimeError):
@@ -181,9 +183,15 @@ def _declare(lib):
                                          P, c_int64, P, P, P, P, P, P, P, c_size_t, P]),
         "gpk_launch_plan": (c_int, [POINTER(GpkLayout), c_int32, c_int32, c_int32, P, c_int64, POINTER(c_int64),
                                     POINTER(c_int64)]),
+        "gpk_mse_grad_workspace_bytes": (c_size_t, [POINTER(GpkKdesc), POINTER(GpkLayout)]),
+        "gpk_mse_backward": (c_int, [POINTER(GpkKdesc), POINTER(GpkLayout), P, c_int64, P, c_int64, P, c_int64, P,
+                                     c_int64, P, P, P, P, P, P, P, P, c_size_t, P]),
+        "gpk_mse_grad": (c_int, [POINTER(GpkKdesc), POINTER(GpkLayout), P, c_int64, P, c_int64, P, c_int64, P, c_int64,
+                                 P, c_int64, P, c_int64, P, P, P, P, P, P, P, P, c_size_t, P]),
     }
     for name, (res, args) in sig.items():
         if (name in ("gpk_op_supported", "gpk_launch_plan") or name in RAGGED_GRAD_ENTRIES or
+                name in MSE_GRAD_ENTRIES or
                 name.startswith(("gpk_mean_", "gpk_fit_"))) and not hasattr(lib, name):
             continue  # (a library built before the entry existed: *op_supported() / fit_supported() then say no)
         fn = getattr(lib, name)
@@ -242,6 +250,20 @@ def ragged_grad_supported(library=None) -> bool:
     it still loads, and engine.RaggedInverseFactorization raises NativeUnavailable."""
     L = library if library is not None else load_library()
     return all(hasattr(L, n) for n in RAGGED_GRAD_ENTRIES)
+
+
+def mse_grad_supported(library=None) -> bool:
+    """Whether the library has the held-out MSE entries (gpk_mse_grad_workspace_bytes, gpk_mse_backward, gpk_mse_grad;
+    added without a new ABI number); False for one built before they existed -- it still loads, and the engine's
+    mse_gradient calls raise NativeUnavailable."""
+    L = library if library is not None else load_library()
+    return all(hasattr(L, n) for n in MSE_GRAD_ENTRIES)
+
+
+def require_mse_grad(library=None):
+    if not mse_grad_supported(library):
+        raise NativeUnavailable("this libgpk.so was built before the held-out MSE entries (gpk_mse_grad and its kin) "
+                                "existed: rebuild it")
 
 
 def fit_state_bytes(n_par: int, batch: int, opts: "GpkFitOpts" = None) -> int:

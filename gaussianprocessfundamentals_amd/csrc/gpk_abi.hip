@@ -1099,6 +1099,141 @@ int gpk_nlml_grad_ragged(const gpk_kdesc* kd, const gpk_layout* lay, const doubl
                          stream);
 }
 
+// ------------------------------------------------------------------------- held-out MSE and its gradient
+// workspace: [batch][2][n_pad] right-hand sides / solutions, [batch][m] residuals, [batch][tiles][n_hyp + 1] partials
+static size_t mse_rhs_elems(const gpk_layout* lay) { return (size_t)lay->batch * 2 * (size_t)lay->n_pad; }
+static size_t mse_res_elems(const gpk_layout* lay) { return (size_t)lay->batch * (size_t)lay->m; }
+
+size_t gpk_mse_grad_workspace_bytes(const gpk_kdesc* kd, const gpk_layout* lay) {
+  if (!kd || !lay || lay->n <= 0 || lay->m <= 0 || lay->batch <= 0) return 0;
+  if (!valid_kdesc(kd, lay->d)) return 0;  // (gpk_mse_backward refuses such a program: no workspace to size)
+  return (mse_rhs_elems(lay) + mse_res_elems(lay) +
+          (size_t)lay->batch * (size_t)mse_tiles(lay->n, lay->m) * (size_t)(kd->n_hyp + 1)) * sizeof(double);
+}
+
+int gpk_mse_backward(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_dev, int64_t hyp_stride,
+                     const double* X, int64_t x_bstride, const double* Xs, int64_t xs_bstride, const double* ys,
+                     int64_t ys_bstride, const int64_t* n_dev, const int64_t* m_dev, const void* W, const void* Winv,
+                     const int32_t* info_dev, double* out_dev, double* grad_dev, void* work, size_t work_bytes,
+                     void* stream) {
+  if (int e = check_layout(lay)) return e == -1 ? fail_arg(2, "layout (use gpk_plan)") : e;
+  if (lay->m < 1) return fail_arg(2, "the MSE needs a layout planned with m >= 1 test points");
+  if (lay->dtype != GPK_F64) return fail_arg(30, "the MSE gradient is fp64 only (layout planned with GPK_F32)");
+  if (!valid_kdesc(kd, lay->d)) return fail_arg(1, "kernel descriptor");
+  if (!hyp_dev && kd->n_hyp > 0) return fail_arg(3, "hyp_dev");
+  if (!X) return fail_arg(5, "X");
+  if (!Xs) return fail_arg(7, "Xs");
+  if (!ys) return fail_arg(9, "ys");
+  if ((n_dev == nullptr) != (m_dev == nullptr)) return fail_arg(11, "n_dev and m_dev: both or neither");
+  if (!W) return fail_arg(13, "W");
+  if (!Winv) return fail_arg(14, "Winv");
+  if (!info_dev) return fail_arg(15, "info_dev");
+  if (!out_dev) return fail_arg(16, "out_dev");
+  if (!grad_dev) return fail_arg(17, "grad_dev");
+  if (!work || work_bytes < gpk_mse_grad_workspace_bytes(kd, lay))
+    return fail_arg(18, "work (see gpk_mse_grad_workspace_bytes)");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  MseArgs g;
+  memset(&g, 0, sizeof(g));
+  g.W = static_cast<const double*>(W);
+  g.ld = lay->ld;
+  g.w_bs = lay->w_batch_stride;
+  g.n = lay->n;
+  g.m = lay->m;
+  g.n_pad = lay->n_pad;
+  g.y_row = lay->y_row;
+  g.hyp = hyp_dev;
+  g.hyp_stride = hyp_stride;
+  g.X = X;
+  g.x_bs = x_bstride;
+  g.Xs = Xs;
+  g.xs_bs = xs_bstride;
+  g.ys = ys;
+  g.ys_bs = ys_bstride;
+  g.d = (int32_t)lay->d;
+  g.dp = (lay->d % 2 == 0) ? (int32_t)lay->d + 1 : (int32_t)lay->d;
+  g.ntr = (lay->n + ATILE - 1) / ATILE;
+  g.nte = (lay->m + ATILE - 1) / ATILE;
+  g.rhs = static_cast<double*>(work);
+  g.res = g.rhs + mse_rhs_elems(lay);
+  g.part = g.res + mse_res_elems(lay);
+  g.out = out_dev;
+  g.grad = grad_dev;
+  g.info = info_dev;
+  g.nb = n_dev;
+  g.mb = m_dev;
+  adjoint_masks(*kd, g.adj_mask);
+  // (timing classes: the residual kernel is this objective's read-out, class 4; the solves 5; the tile pass 6)
+  GPK_HIP(timed(4, 0.0, 0.0, s, [&] { return launch_mse_residual(g, lay->batch, s); }), "mse residual");
+  // q = L^-T c and alpha = L^-T z: the batched backward solve once per right-hand side (member stride 2 n_pad)
+  const int64_t nblk = lay->n_pad / NB;
+  TrsvArgs t;
+  t.W = W;
+  t.ld = lay->ld;
+  t.w_bs = lay->w_batch_stride;
+  t.Winv = Winv;
+  t.inv_bs = lay->inv_batch_stride;
+  t.x_bs = 2 * lay->n_pad;
+  t.n_pad = lay->n_pad;
+  t.trans = 1;
+  t.n_valid = lay->n_pad;
+  for (int rhs = 0; rhs < 2; ++rhs) {
+    t.x = g.rhs + rhs * lay->n_pad;
+    for (int64_t i = 0; i < nblk; ++i) {
+      t.kblk = nblk - 1 - i;
+      GPK_HIP(timed(5, 0.0, 0.0, s, [&] { return launch_trsv_diag(t, GPK_F64, lay->batch, s); }), "mse trsv_diag");
+      GPK_HIP(timed(5, 0.0, 0.0, s, [&] { return launch_trsv_update(t, GPK_F64, lay->batch, s); }),
+              "mse trsv_update");
+    }
+  }
+  GPK_HIP(timed(6, 0.0, 0.0, s, [&] { return launch_mse_tiles(*kd, g, lay->batch, s); }), "mse tiles");
+  return 0;
+}
+
+int gpk_mse_grad(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_dev, int64_t hyp_stride,
+                 const double* noise_dev, int64_t noise_stride, const double* X, int64_t x_bstride, const double* Xs,
+                 int64_t xs_bstride, const double* y, int64_t y_bstride, const double* ys, int64_t ys_bstride,
+                 const int64_t* n_dev, const int64_t* m_dev, void* W, void* Winv, int32_t* info_dev, double* out_dev,
+                 double* grad_dev, void* work, size_t work_bytes, void* stream) {
+  if (int e = check_layout(lay)) return e == -1 ? fail_arg(2, "layout (use gpk_plan)") : e;
+  if (lay->m < 1) return fail_arg(2, "the MSE needs a layout planned with m >= 1 test points");
+  if (lay->dtype != GPK_F64) return fail_arg(30, "the MSE gradient is fp64 only (layout planned with GPK_F32)");
+  if (!valid_kdesc(kd, lay->d)) return fail_arg(1, "kernel descriptor");
+  if (!hyp_dev && kd->n_hyp > 0) return fail_arg(3, "hyp_dev");
+  if (!noise_dev) return fail_arg(5, "noise_dev");
+  if (!X) return fail_arg(7, "X");
+  if (!Xs) return fail_arg(9, "Xs");
+  if (!y) return fail_arg(11, "y");
+  if (!ys) return fail_arg(13, "ys");
+  if ((n_dev == nullptr) != (m_dev == nullptr)) return fail_arg(15, "n_dev and m_dev: both or neither");
+  if (!W) return fail_arg(17, "W");
+  if (!Winv) return fail_arg(18, "Winv");
+  if (!info_dev) return fail_arg(19, "info_dev");
+  if (!out_dev) return fail_arg(20, "out_dev");
+  if (!grad_dev) return fail_arg(21, "grad_dev");
+  if (!work || work_bytes < gpk_mse_grad_workspace_bytes(kd, lay))
+    return fail_arg(22, "work (see gpk_mse_grad_workspace_bytes)");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  GPK_HIP(hipMemsetAsync(info_dev, 0, sizeof(int32_t) * lay->batch, s), "memset info");
+  int e;
+  if (n_dev) {
+    e = gpk_assemble_ragged(kd, lay, hyp_dev, hyp_stride, noise_dev, noise_stride, X, x_bstride, Xs, xs_bstride, y,
+                            y_bstride, n_dev, m_dev, W, stream);
+    if (e) return e;
+    e = gpk_potrf_aug_ragged(lay, W, Winv, info_dev, n_dev, m_dev, stream);
+  } else {
+    e = gpk_assemble(kd, lay, hyp_dev, hyp_stride, noise_dev, noise_stride, X, x_bstride, Xs, xs_bstride, nullptr, 0,
+                     y, y_bstride, W, stream);
+    if (e) return e;
+    e = gpk_potrf_aug(lay, W, Winv, info_dev, stream);
+  }
+  if (e) return e;
+  // (the read-out: gpk_mse_backward's first kernel reads -mu from the corner's y row, where gpk_finalize reads it;
+  // every argument it checks was checked above)
+  return gpk_mse_backward(kd, lay, hyp_dev, hyp_stride, X, x_bstride, Xs, xs_bstride, ys, ys_bstride, n_dev, m_dev, W,
+                          Winv, info_dev, out_dev, grad_dev, work, work_bytes, stream);
+}
+
 int gpk_kernel_matrix(const gpk_kdesc* kd, const double* hyp_dev, int dtype, int uplo,
                       const double* X, int64_t n, const double* Y, int64_t m, int32_t d,
                       double diag_add, void* K, int64_t ldk, void* stream) {

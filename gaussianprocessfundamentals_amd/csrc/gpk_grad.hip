@@ -1,11 +1,13 @@
-// Reverse mode of the kernel program: the LML gradient (gpk_nlml_grad: grad_kernel) and the adjoints of a rectangular
-// kernel matrix (gpk_kernel_vjp: vjp_kernel).  Both walk 64 x 64 tiles staged as the K build stages them (gpk_stage.h)
-// and re-evaluate the program per element with the reference's literal formulas (base_values, gpk_kernels.h).
-// Two things are written twice here on purpose, in the same words, and a change to one belongs in the other
-// (DESIGN 18, profiles/grad_split_codegen.txt, profiles/grad_split_ab.txt):
-// - the two kernels' loops over the program's leaves (adjoint product over adj_mask, base_partials, the leaf's
+// Reverse mode of the kernel program: the LML gradient (gpk_nlml_grad: grad_kernel), the adjoints of a rectangular
+// kernel matrix (gpk_kernel_vjp: vjp_kernel) and the gradient of the held-out mean squared error (gpk_mse_backward:
+// mse_tile_kernel).  All walk 64 x 64 tiles staged as the K build stages them (gpk_stage.h) and re-evaluate the
+// program per element with the reference's literal formulas (base_values, gpk_kernels.h).
+// Two things are written more than once here on purpose, in the same words, and a change to one belongs in the others
+// (DESIGN 18 and 23, profiles/grad_split_codegen.txt, profiles/grad_split_ab.txt):
+// - the three kernels' loops over the program's leaves (adjoint product over adj_mask, base_partials, the leaf's
 //   node_params slots, the four-wave reduction into red, the window leaf's add to a shared bound): as one function
-//   template the body takes vjp_kernel<true>, which sits at exactly 256 VGPRs, to one wave per SIMD;
+//   template the body takes vjp_kernel<true>, which sits at exactly 256 VGPRs, to one wave per SIMD (mse_tile_kernel's
+//   copy is the third, under the same rule: it leaves the other two kernels' code as it was);
 // - the distance and Matern prologues of base_partials and base_input_partials: as shared helpers they compute the
 //   same bits but kernel_vjp measured 1 to 2 % slower than with this text.
 #include <string.h>
@@ -593,7 +595,281 @@ __global__ __launch_bounds__(256) void vjp_reduce_kernel(const double* part, int
   if (tid == 0) out[p] = scale * red[0];
 }
 
+// ================================================================================ MSE gradient
+// f = (1 / m) r^T r, r = mu - y_test, mu = V z, of a factored augmented matrix with m test rows (V = K_s^T L^-T in the
+// test rows, z = L^-1 y in the y row, -mu in the corner's y row).  With alpha = L^-T z and q = L^-T (V^T r):
+//   d f / d theta = (2 / m) [ sum_it alpha_i r_t d k(x_i, x*_t) / d theta - sum_ij q_i alpha_j d k(x_i, x_j) / d theta ],
+//   d f / d noise = -(2 / m) q^T alpha
+// -- both weights rank one, K^-1 never formed.  mse_residual_kernel computes r, f and the two right-hand
+// sides; the batched backward solve gives q and alpha; mse_tile_kernel sums the weighted partials per tile;
+// mse_reduce_kernel adds the tiles in a fixed order.
+
+// r_b, sum r^2 and the right-hand sides c = V^T r, z of member b: workgroup x takes 256 columns j, re-reads r in chunks
+// of 256 test rows (LDS) and accumulates c_j down the test rows in row order; workgroup 0 also writes r and the value
+template <bool RAG>
+__global__ __launch_bounds__(256) void mse_residual_kernel(MseArgs g) {
+  __shared__ double rs[256];
+  __shared__ double red[256];
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const int64_t j = (int64_t)blockIdx.x * 256 + tid;
+  int64_t nn = g.n, mm = g.m;
+  if constexpr (RAG) {
+    nn = g.nb[b];
+    mm = g.mb[b];
+  }
+  const double* W = g.W + (int64_t)b * g.w_bs;
+  const double* ys = g.ys + (int64_t)b * g.ys_bs;
+  double cj = 0.0, sq = 0.0;
+  for (int64_t t0 = 0; t0 < g.m; t0 += 256) {  // (the layout's m: workgroup-uniform trip count)
+    const int64_t tt = t0 + tid;
+    const double r = tt < mm ? -W[g.y_row * g.ld + g.n_pad + tt] - ys[tt] : 0.0;  // the corner's y row holds -mu
+    rs[tid] = r;
+    sq += r * r;
+    if (blockIdx.x == 0 && tt < g.m) g.res[(int64_t)b * g.m + tt] = r;
+    __syncthreads();
+    const int kn = (int)((mm - t0) < 256 ? (mm - t0) : 256);
+    if (j < nn)
+      for (int k = 0; k < kn; ++k) cj = fma(W[(g.n_pad + t0 + k) * g.ld + j], rs[k], cj);
+    __syncthreads();
+  }
+  if (j < g.n_pad) {
+    double* rhs = g.rhs + (int64_t)b * 2 * g.n_pad;
+    rhs[j] = j < nn ? cj : 0.0;
+    rhs[g.n_pad + j] = j < nn ? W[g.y_row * g.ld + j] : 0.0;
+  }
+  if (blockIdx.x != 0) return;
+  red[tid] = sq;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (tid < w) red[tid] += red[tid + w];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    g.out[b * 4 + 0] = g.info[b] != 0 ? INFINITY : red[0] / (double)mm;
+    g.out[b * 4 + 1] = red[0];
+    g.out[b * 4 + 2] = (double)mm;
+    g.out[b * 4 + 3] = (double)nn;
+  }
+}
+
+// One 64 x 64 tile per workgroup: tiles t < ntr (ntr + 1) / 2 are the lower TRAIN x TRAIN tiles (weight
+// -(q_i alpha_j + q_j alpha_i) strictly below the diagonal, -q_i alpha_i on it -- whose sum is also the noise partial
+// -- 0 above), the nte * ntr tiles after them TEST x TRAIN (weight r_t alpha_j; rows = test points).  The q, alpha and r
+// slices of the tile's edges are staged in LDS once; no matrix is read.  RAG: member b's own n_b / m_b bound the
+// staging, and a tile wholly in padding writes plain zeros for its n_hyp + 1 partials and evaluates nothing (as
+// grad_kernel<.., RAG>).  The leaf loop is grad_kernel's, in the same words (see the top of this file).
+template <bool RQL, bool RAG>
+__global__ __launch_bounds__(256) void mse_tile_kernel(gpk_kdesc kd, AsmArgs a, MseArgs g) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  const int slot_stride = ATILE * a.dp;
+  double* hyp_s = smem;                                  // GPK_MAX_HYP
+  double* q_r = hyp_s + GPK_MAX_HYP;                     // q (TEST rows: r) of the tile rows
+  double* al_r = q_r + ATILE;                            // alpha of the tile rows (TEST rows: unused)
+  double* q_c = al_r + ATILE;                            // q, alpha of the tile columns
+  double* al_c = q_c + ATILE;
+  double* red = al_c + ATILE;                            // [4 waves][GNP + 1]
+  double* prow = red + 4 * (GNP + 1);
+  double* pcol = prow + (1 + kd.n_ard) * slot_stride;
+  double* vals = pcol + (1 + kd.n_ard) * slot_stride;   // [n_nodes][256] node values (MUL trees)
+
+  const int b = blockIdx.y;
+  const int64_t t = blockIdx.x;
+  const int64_t ntri = g.ntr * (g.ntr + 1) / 2;
+  const bool test = t >= ntri;
+  int64_t ti, tj;
+  if (test) {
+    ti = (t - ntri) / g.ntr;
+    tj = (t - ntri) - ti * g.ntr;
+  } else {
+    int64_t r = (int64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+    while (r * (r + 1) / 2 > t) --r;
+    while ((r + 1) * (r + 2) / 2 <= t) ++r;
+    ti = r;
+    tj = t - r * (r + 1) / 2;
+  }
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int np1 = kd.n_hyp + 1;
+  double* part = g.part + ((int64_t)b * gridDim.x + t) * np1;
+  int64_t nn = g.n, mm = g.m;
+  if constexpr (RAG) {
+    nn = g.nb[b];
+    mm = g.mb[b];
+    // (workgroup-uniform) rows or columns wholly past the member's points: every weight is zero
+    if (test ? (ti * ATILE >= mm || tj * ATILE >= nn) : (ti * ATILE >= nn)) {
+      for (int e = tid; e < np1; e += 256) part[e] = 0.0;
+      return;
+    }
+  }
+  const double* hyp_g = g.hyp + (int64_t)b * g.hyp_stride;
+  for (int e = tid; e < kd.n_hyp; e += 256) hyp_s[e] = hyp_g[e];
+  const int64_t gi0 = test ? g.n_pad + ti * ATILE : ti * ATILE, gj0 = tj * ATILE;
+  if (tid < 2 * ATILE) {
+    const int e = tid & (ATILE - 1);
+    const double* rhs = g.rhs + (int64_t)b * 2 * g.n_pad;
+    if (tid < ATILE && test) {
+      const int64_t tt = ti * ATILE + e;
+      q_r[e] = tt < mm ? g.res[(int64_t)b * g.m + tt] : 0.0;
+      al_r[e] = 0.0;
+    } else {
+      const int64_t gg = (tid < ATILE ? gi0 : gj0) + e;
+      const bool in = gg < nn;
+      (tid < ATILE ? q_r : q_c)[e] = in ? rhs[gg] : 0.0;
+      (tid < ATILE ? al_r : al_c)[e] = in ? rhs[g.n_pad + gg] : 0.0;
+    }
+  }
+  __syncthreads();
+  stage_points(kd, a, hyp_s, prow, gi0, b, true, slot_stride);
+  stage_points(kd, a, hyp_s, pcol, gj0, b, false, slot_stride);
+  __syncthreads();
+
+  const int c = lane;
+  const int64_t gj = gj0 + c;
+  // weight of this thread's element in tile row rr (the strictly lower triangle stands for both halves)
+  auto qval = [&](int rr) -> double {
+    if (test) return q_r[rr] * al_c[c];
+    const int64_t gi = gi0 + rr;
+    if (gi >= nn || gj > gi) return 0.0;
+    const double qq = q_r[rr] * al_c[c];
+    return gi == gj ? -qq : -(qq + q_c[c] * al_r[rr]);
+  };
+  double noise_acc = 0.0;  // d K / d noise = I: the diagonal of the weighted matrix
+  if (!test && ti == tj && (c & 3) == wave) noise_acc = qval(c);
+
+  for (int qn = 0; qn < kd.n_nodes; ++qn) {
+    const gpk_node nd = kd.nodes[qn];
+    if (nd.op == GPK_OP_ADD || nd.op == GPK_OP_MUL) continue;
+    const uint32_t mask = g.adj_mask[qn];
+    const int off = (nd.flags & GPK_NODE_ARD) ? (nd.ard_slot + 1) * slot_stride : 0;
+    double acc[GNP];
+#pragma unroll
+    for (int k = 0; k < GNP; ++k) acc[k] = 0.0;
+#pragma unroll 1
+    for (int k = 0; k < ATILE / 4; ++k) {
+      const int rr = wave + 4 * k;
+      const double qk = qval(rr);
+      if (qk == 0.0) continue;
+      double adj = 1.0;
+      if (mask != 0u) {
+        eval_nodes<RQL>(kd, hyp_s, prow + rr * a.dp, pcol + c * a.dp, slot_stride, a.d, vals + tid);
+#pragma unroll 1
+        for (int q = 0; q < kd.n_nodes; ++q)
+          if (mask & (1u << q)) adj *= vals[q * 256 + tid];
+      }
+      base_partials<RQL>(nd, hyp_s, prow + off + rr * a.dp, pcol + off + c * a.dp, a.d, qk * adj, acc);
+    }
+    // hyperparameter slots of this node (node_params): ARD l_0..l_{d-1} then sg (stored at acc[GPK_MAX_DIM])
+    const bool ard = (nd.flags & GPK_NODE_ARD) != 0;
+    const bool vec = ard || nd.op == GPK_OP_LIN;  // d vector entries (ARD l, LIN c), then sg
+    const bool win = nd.op == GPK_OP_CPW;         // its one or two bounds, no sg
+    const bool scaled = (nd.flags & GPK_NODE_SCALED) != 0;
+    const bool sg_moved = vec && scaled;
+    const int np = node_params(nd, a.d);
+#pragma unroll
+    for (int k = 0; k < GNP; ++k) {
+      if (k < np) {
+        const double sres = wave_sum((sg_moved && k == a.d) ? acc[GPK_MAX_DIM] : acc[k]);
+        if (lane == 0) red[wave * (GNP + 1) + k] = sres;
+      }
+    }
+    __syncthreads();
+    if (win) {
+      // adjacent window leaves share a bound's slot (cp_i: upper bound of window i, lower bound of window i + 1): the
+      // later leaf adds to what the earlier one wrote.  Thread s owns slot s for every window leaf, so the sum is
+      // that thread's own read-modify-write in program order (deterministic)
+      const int k = tid - nd.hyp_offset;
+      if (k >= 0 && k < np) {
+        const double sres = red[k] + red[(GNP + 1) + k] + red[2 * (GNP + 1) + k] + red[3 * (GNP + 1) + k];
+        part[tid] = cp_slot_written(kd, qn, tid) ? part[tid] + sres : sres;
+      }
+    } else if (tid < np) {
+      part[nd.hyp_offset + tid] = red[tid] + red[(GNP + 1) + tid] + red[2 * (GNP + 1) + tid] +
+                                  red[3 * (GNP + 1) + tid];
+    }
+    __syncthreads();
+  }
+  const double ns = wave_sum(noise_acc);
+  if (lane == 0) red[wave * (GNP + 1) + GNP] = ns;
+  __syncthreads();
+  if (tid == 0)
+    part[kd.n_hyp] = red[GNP] + red[(GNP + 1) + GNP] + red[2 * (GNP + 1) + GNP] + red[3 * (GNP + 1) + GNP];
+}
+
+// grad[b][p] = (2 / m_b) sum over tiles (fixed order); NaN where the factorisation failed
+__global__ __launch_bounds__(256) void mse_reduce_kernel(MseArgs g, int64_t ntile, int np1) {
+  __shared__ double red[256];
+  const int p = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  const double* part = g.part + (int64_t)b * ntile * np1 + p;
+  double s = 0.0;
+  for (int64_t t = tid; t < ntile; t += 256) s += part[t * np1];
+  red[tid] = s;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (tid < w) red[tid] += red[tid + w];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const double mm = (double)(g.mb ? g.mb[b] : g.m);
+    g.grad[(int64_t)b * np1 + p] = g.info[b] != 0 ? NAN : (2.0 / mm) * red[0];
+  }
+}
+
 }  // namespace
+
+int64_t mse_tiles(int64_t n, int64_t m) {
+  const int64_t ntr = (n + ATILE - 1) / ATILE, nte = (m + ATILE - 1) / ATILE;
+  return ntr * (ntr + 1) / 2 + nte * ntr;
+}
+
+hipError_t launch_mse_residual(const MseArgs& g, int32_t batch, hipStream_t s) {
+  dim3 grid((unsigned)((g.n_pad + 255) / 256), (unsigned)batch);
+  if (g.nb != nullptr)
+    hipLaunchKernelGGL(mse_residual_kernel<true>, grid, dim3(256), 0, s, g);
+  else
+    hipLaunchKernelGGL(mse_residual_kernel<false>, grid, dim3(256), 0, s, g);
+  return hipGetLastError();
+}
+
+hipError_t launch_mse_tiles(const gpk_kdesc& kd, const MseArgs& g, int32_t batch, hipStream_t s) {
+  // the staging helpers read the points through an augmented-layout AsmArgs (test rows from Xs)
+  AsmArgs a;
+  memset(&a, 0, sizeof(a));
+  a.hyp = g.hyp;
+  a.hyp_stride = g.hyp_stride;
+  a.X = g.X;
+  a.x_bs = g.x_bs;
+  a.Xs = g.Xs;
+  a.xs_bs = g.xs_bs;
+  a.n = g.n;
+  a.m = g.m;
+  a.n_pad = g.n_pad;
+  a.y_row = g.y_row;
+  a.d = g.d;
+  a.dp = g.dp;
+  a.nb = g.nb;  // ragged (NULL: uniform): member_n / member_m bound the points stage_points reads
+  a.mb = g.mb;
+  const int64_t ntile = g.ntr * (g.ntr + 1) / 2 + g.nte * g.ntr;
+  bool has_mul = false;
+  for (int q = 0; q < kd.n_nodes; ++q) has_mul |= g.adj_mask[q] != 0u;
+  const size_t lds = sizeof(double) * (GPK_MAX_HYP + 4 * ATILE + 4 * (GNP + 1) +
+                                       2 * (size_t)(1 + kd.n_ard) * ATILE * a.dp +
+                                       (has_mul ? (size_t)kd.n_nodes * 256 : 0));
+  dim3 grid((unsigned)ntile, (unsigned)batch, 1);
+  // (a program with a rational quadratic leaf: the instantiation that carries the leaf's code, rq_leaves)
+  const bool rq = rq_leaves(kd) > 0;
+  const auto tile = g.nb != nullptr ? (rq ? mse_tile_kernel<true, true> : mse_tile_kernel<false, true>)
+                                    : (rq ? mse_tile_kernel<true, false> : mse_tile_kernel<false, false>);
+  {
+    hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(tile), lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(tile, grid, dim3(256), lds, s, kd, a, g);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(mse_reduce_kernel, dim3((unsigned)(kd.n_hyp + 1), (unsigned)batch), dim3(256), 0, s, g, ntile,
+                     kd.n_hyp + 1);
+  return hipGetLastError();
+}
 
 size_t vjp_workspace_elems(const gpk_kdesc& kd, int64_t n, int64_t m, int32_t d, bool want_z) {
   const int64_t tr = (n + ATILE - 1) / ATILE, tc = (m + ATILE - 1) / ATILE;

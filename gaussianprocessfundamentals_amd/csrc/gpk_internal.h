@@ -233,6 +233,37 @@ struct GradArgs {
                        // uniform instantiations read every other field where they did
 };
 
+// gpk_mse_backward (gpk_grad.hip): gradient of the held-out mean squared error from a factored augmented matrix with
+// m test rows.  rhs holds, per member, the two right-hand sides of the backward solves and then their solutions:
+// slot 0 c = V^T r -> q = L^-T c, slot 1 z -> alpha = L^-T z (entries at and past the member's n_b zero).
+struct MseArgs {
+  const double* W;     // factored augmented matrix (fp64), test rows n_pad .. n_pad + m - 1
+  int64_t ld;
+  int64_t w_bs;
+  int64_t n, m, n_pad, y_row;
+  const double* hyp;
+  int64_t hyp_stride;
+  const double* X;
+  int64_t x_bs;
+  const double* Xs;
+  int64_t xs_bs;
+  const double* ys;    // test targets
+  int64_t ys_bs;
+  int32_t d;
+  int32_t dp;
+  int64_t ntr, nte;    // 64-tiles of the training / test points: ntr (ntr + 1) / 2 lower TRAIN x TRAIN tiles, then
+                       // nte * ntr TEST x TRAIN tiles (test tile major)
+  double* rhs;         // [batch][2][n_pad]
+  double* res;         // [batch][m] residual r = mu - ys (0 past the member's m_b)
+  double* part;        // [batch][tiles][n_hyp + 1] per-tile partial sums
+  double* out;         // [batch][4]: mse, sum r^2, m_b, n_b
+  double* grad;        // [batch][n_hyp + 1]
+  const int32_t* info;
+  uint32_t adj_mask[GPK_MAX_NODES];
+  const int64_t* nb;   // ragged batches: training / test points of member b (NULL: n / m)
+  const int64_t* mb;
+};
+
 // gpk_kernel_vjp (gpk_grad.hip): adjoints of K(X, Z) = kernel(X, Z) for a weight matrix G [n, ldg]
 struct VjpArgs {
   const double* hyp;   // [n_hyp] device
@@ -273,6 +304,9 @@ hipError_t launch_finalize(const FinArgs& a, int dtype, int32_t batch, hipStream
 hipError_t launch_chain(const ChainArgs& a, int dtype, int grid, hipStream_t s);
 hipError_t chain_timeouts_read(int64_t* out);  // timed-out persistent launches on this device (synchronous)
 hipError_t launch_grad(const gpk_kdesc& kd, const GradArgs& g, int dtype, int32_t batch, hipStream_t s);
+int64_t mse_tiles(int64_t n, int64_t m);  // tiles of the MSE gradient's tile pass
+hipError_t launch_mse_residual(const MseArgs& g, int32_t batch, hipStream_t s);
+hipError_t launch_mse_tiles(const gpk_kdesc& kd, const MseArgs& g, int32_t batch, hipStream_t s);
 size_t vjp_workspace_elems(const gpk_kdesc& kd, int64_t n, int64_t m, int32_t d, bool want_z);
 hipError_t launch_vjp(const gpk_kdesc& kd, const VjpArgs& g, const double* X, int64_t n, const double* Z, int64_t m,
                       int32_t d, double* grad_hyp, double* grad_z, hipStream_t s);

@@ -364,6 +364,7 @@ class AugmentedFactorization:
         self.kd = None
         self.done = False
         self.shape_key = None
+        self._mse_work = self._mse_out = self._mse_grad = self._mse_operands = None
 
     # -- result buffers: every read settles a pending persistent run first ---------------------
     @property
@@ -470,6 +471,8 @@ class AugmentedFactorization:
             self.done = True
             return self
         self.info.zero_()
+        # (what mse_gradient needs of this run: kernel rows only -- explicit extra rows have no test points)
+        self._mse_operands = (kd, hyp, hyp_stride, X, x_bstride, Xs, xs_bstride) if E is None else None
         nat.check(L.gpk_assemble(ctypes.byref(kd), ctypes.byref(lay), nat.ptr(hyp), hyp_stride,
                                  nat.ptr(noise), noise_stride, nat.ptr(X), x_bstride,
                                  nat.ptr(Xs), xs_bstride, nat.ptr(E), e_bstride,
@@ -544,6 +547,104 @@ class AugmentedFactorization:
     def alpha(self, b: int = 0) -> torch.Tensor:
         """alpha = L^-T z = (K + noise I)^-1 y of member b (see :meth:`alphas`)."""
         return self.alphas()[b]
+
+    # -- held-out MSE and its gradient (gpk_mse_backward / gpk_mse_grad) ------------------------
+    def _mse_buffers(self, kd):
+        """(out [B * 4], grad [B, n_hyp + 1], work) of the MSE pass: the workspace is kept between calls, the two
+        result buffers are the caching allocator's per evaluation (earlier views stay valid, as _fresh_out)."""
+        nat.require_mse_grad(self.L)
+        if self.m < 1:
+            raise ValueError("the MSE needs test points: this factorisation was planned with m = 0")
+        if self.code != nat.GPK_F64:
+            raise NotImplementedError("the MSE gradient is fp64 only")
+        dev = self._W.device
+        need = int(self.L.gpk_mse_grad_workspace_bytes(ctypes.byref(kd), ctypes.byref(self.layout)))
+        if need == 0:
+            raise ValueError("the kernel program is not valid for dimension %d" % self.d)
+        if self._mse_work is None or self._mse_work.numel() * 8 < need:
+            self._mse_work = torch.empty(need // 8, dtype=torch.float64, device=dev)
+        self._mse_out = torch.empty(self.batch * 4, dtype=torch.float64, device=dev)
+        self._mse_grad = torch.empty((self.batch, kd.n_hyp + 1), dtype=torch.float64, device=dev)
+        return self._mse_out, self._mse_grad, self._mse_work
+
+    def _ragged_counts(self):
+        """(n_dev, m_dev) pointers of a ragged batch; (None, None) here."""
+        return None, None
+
+    def mse_gradient(self, ys: torch.Tensor, ys_bstride: int = 0):
+        """The MSE pass alone on the last :meth:`run` (test points as extra rows): (mse [B], grad [B, n_hyp + 1])
+        device views, the gradient laid out as InverseFactorization.gradient() (noise last); +inf / NaN where
+        info != 0.  ``ys``: test targets, member b's at ys[b * ys_bstride:].  Enqueues only (a pending persistent run is
+        settled first, like every read of W)."""
+        ops = self._mse_operands if self.done else None
+        if ops is None:
+            raise RuntimeError("run(..., Xs=...) with test points first")
+        kd, hyp, hyp_stride, X, x_bstride, Xs, xs_bstride = ops
+        out, grad, work = self._mse_buffers(kd)
+        dev = self._W.device
+        _check_operand("y_test", ys, ys_bstride, self.m, self.batch, dev)
+        n_ptr, m_ptr = self._ragged_counts()
+        nat.check(self.L.gpk_mse_backward(
+            ctypes.byref(kd), ctypes.byref(self.layout), nat.ptr(hyp), hyp_stride, nat.ptr(X), x_bstride,
+            nat.ptr(Xs), xs_bstride, nat.ptr(ys), ys_bstride, n_ptr, m_ptr, nat.ptr(self.W), nat.ptr(self.Winv),
+            nat.ptr(self.info), nat.ptr(out), nat.ptr(grad), nat.ptr(work), work.numel() * 8,
+            nat.stream_handle(dev)), "gpk_mse_backward")
+        self._keep_mse = ys
+        return out.view(self.batch, 4)[:, 0], grad
+
+    def run_mse(self, kd: nat.GpkKdesc, hyp: torch.Tensor, hyp_stride: int, noise: torch.Tensor, noise_stride: int,
+                X: torch.Tensor, x_bstride: int, y: torch.Tensor, y_bstride: int, Xs: torch.Tensor, xs_bstride: int,
+                ys: torch.Tensor, ys_bstride: int):
+        """K build + factorisation + MSE value and gradient as one call (gpk_mse_grad); asynchronous, a persistent
+        run is verified at the first read (:meth:`mse`, :meth:`mse_grad`, info).  ``unsettled_mse()`` gives the views
+        without that."""
+        args = (kd, hyp, hyp_stride, noise, noise_stride, X, x_bstride, y, y_bstride, Xs, xs_bstride, ys, ys_bstride)
+        self._pending = None
+        self._run_mse_once(*args)
+        self._defer_verify(lambda: self._run_mse_once(*args))
+        return self
+
+    def _run_mse_once(self, kd, hyp, hyp_stride, noise, noise_stride, X, x_bstride, y, y_bstride, Xs, xs_bstride,
+                      ys, ys_bstride):
+        B, n, m, d = self.batch, self.n, self.m, self.d
+        dev = self._W.device
+        self._alphas = None
+        out, grad, work = self._mse_buffers(kd)
+        _check_operand("hyper_parameter", hyp, hyp_stride, kd.n_hyp, B, dev)
+        _check_operand("noise", noise, noise_stride, 1, B, dev)
+        _check_operand("X", X, x_bstride, n * d, B, dev)
+        _check_operand("y", y, y_bstride, n, B, dev)
+        _check_operand("X_test", Xs, xs_bstride, m * d, B, dev)
+        _check_operand("y_test", ys, ys_bstride, m, B, dev)
+        n_ptr, m_ptr = self._ragged_counts()
+        nat.check(self.L.gpk_mse_grad(
+            ctypes.byref(kd), ctypes.byref(self.layout), nat.ptr(hyp), hyp_stride, nat.ptr(noise), noise_stride,
+            nat.ptr(X), x_bstride, nat.ptr(Xs), xs_bstride, nat.ptr(y), y_bstride, nat.ptr(ys), ys_bstride,
+            n_ptr, m_ptr, nat.ptr(self._W), nat.ptr(self._Winv), nat.ptr(self._info), nat.ptr(out), nat.ptr(grad),
+            nat.ptr(work), work.numel() * 8, nat.stream_handle(dev)), "gpk_mse_grad")
+        self._mse_operands = (kd, hyp, hyp_stride, X, x_bstride, Xs, xs_bstride)
+        self._keep_mse = (noise, y, ys)
+        self.kd = kd
+        self.done = True
+        return self
+
+    def mse(self) -> torch.Tensor:
+        """[batch] mean squared errors of the last run_mse / mse_gradient (+inf where info != 0)."""
+        self._settle()
+        if self._mse_out is None:
+            raise RuntimeError("run_mse(...) or mse_gradient(...) first")
+        return self._mse_out.view(self.batch, 4)[:, 0]
+
+    def mse_grad(self) -> torch.Tensor:
+        """[batch, n_hyp + 1] fp64: d mse / d hyp (DFS order), then d mse / d noise."""
+        self._settle()
+        if self._mse_grad is None:
+            raise RuntimeError("run_mse(...) or mse_gradient(...) first")
+        return self._mse_grad
+
+    def unsettled_mse(self):
+        """(mse, gradient, info) device views WITHOUT settling a pending persistent run (see unsettled_results)."""
+        return self._mse_out.view(self.batch, 4)[:, 0], self._mse_grad, self._info
 
     def check_info(self):
         """Raise CholeskyError if any batch member failed (synchronises)."""
@@ -733,8 +834,44 @@ class RaggedFactorization(AugmentedFactorization):
                                         nat.ptr(self.mu) if m else None, nat.ptr(self.var) if m else None, s),
                   "gpk_finalize_ragged")
         self._keep = (X, y, Xs, hyp, nz)  # operands stay alive until the stream has consumed them
+        # (what mse_gradient needs of this run: one program for every member)
+        same = all(bytes(k) == bytes(kds[0]) for k in kds)
+        self._mse_operands = (kds[0], hyp, nat.MAX_HYP, X, n * d, Xs, max(m, 1) * d) if same and m else None
         self.kd = kds
         self.done = True
+        return self
+
+    # -- held-out MSE of a ragged batch ---------------------------------------------------------
+    def _ragged_counts(self):
+        if min(self.test_sizes) < 1:
+            raise ValueError("the MSE needs at least one test point per member (test_sizes %s)" % (self.test_sizes,))
+        return nat.ptr(self.n_dev), nat.ptr(self.m_dev)
+
+    def mse_gradient(self, ys, ys_bstride: Optional[int] = None):
+        """As AugmentedFactorization.mse_gradient for members sharing one kernel program.  ``ys``: one tensor of
+        m_b test targets per member, or a packed [B, m] device tensor (what lies past m_b is not read)."""
+        if isinstance(ys, (list, tuple)):
+            if len(ys) != self.batch:
+                raise ValueError("expected %d test-target vectors, got %d" % (self.batch, len(ys)))
+            packed = torch.zeros((self.batch, self.m), dtype=torch.float64, device=self._W.device)
+            for b, v in enumerate(ys):
+                if v.numel() != self.test_sizes[b]:
+                    raise ValueError("member %d: y_test must hold %d values" % (b, self.test_sizes[b]))
+                packed[b, :self.test_sizes[b]] = v.detach().reshape(-1)
+            ys, ys_bstride = packed, self.m
+        if self.done and self._mse_operands is None and self.m:
+            raise ValueError("mse_gradient needs members that share one kernel program")
+        return super().mse_gradient(ys, self.m if ys_bstride is None else ys_bstride)
+
+    def run_mse_packed(self, kd: nat.GpkKdesc, hyp: torch.Tensor, noise: torch.Tensor, X: torch.Tensor,
+                       y: torch.Tensor, Xs: torch.Tensor, ys: torch.Tensor) -> "RaggedFactorization":
+        """K build + factorisation + MSE value and gradient of a ragged batch whose members share one program, on
+        operands already packed on the device (gpk_mse_grad with n_dev / m_dev): hyp [B, MAX_HYP], noise [B],
+        X [B, n, d], y [B, n], Xs [B, m, d], ys [B, m]; what lies past a member's own counts is not read.  No host
+        round trip; read mse() / mse_grad() / info (ragged batches never take the persistent launch)."""
+        n, m, d = self.n, self.m, self.d
+        self.run_mse(kd, hyp, nat.MAX_HYP, noise, 1, X, n * d, y, n, Xs, m * d, ys, m)
+        self.kd = [kd] * self.batch
         return self
 
     # -- per-member read-out ------------------------------------------------------------------

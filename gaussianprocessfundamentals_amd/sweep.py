@@ -234,6 +234,124 @@ def native_kfold_value_and_gradient(kernel, folds, dtype=None):
     return evaluate
 
 
+def _check_candidates(cands: torch.Tensor, width: int, dev) -> None:
+    if cands.dim() != 2 or int(cands.shape[1]) != width:
+        raise ValueError("candidate rows must have %d values (hyperparameters, then the noise)" % width)
+    if cands.dtype != torch.float64 or cands.device != dev or not cands.is_contiguous():
+        raise ValueError("candidates must be a contiguous float64 tensor on %s" % (dev,))
+
+
+def _check_mse_shapes(X, y, Xs, ys, d=None):
+    """Host-only shape check of one (X, y, X_test, y_test) quadruple; returns (n, m, d)."""
+    if X.dim() != 2 or Xs.dim() != 2 or int(X.shape[0]) < 1:
+        raise ValueError("X must be [n >= 1, d] and X_test [m, d]")
+    n, dd, m = int(X.shape[0]), int(X.shape[1]), int(Xs.shape[0])
+    if int(Xs.shape[1]) != dd or (d is not None and dd != d):
+        raise ValueError("X and X_test must share the dimension %d" % (dd if d is None else d))
+    if m < 1:
+        raise ValueError("the MSE needs at least one test point")
+    if int(y.numel()) != n:
+        raise ValueError("y has %d values, X has %d points" % (int(y.numel()), n))
+    if int(ys.numel()) != m:
+        raise ValueError("y_test has %d values, X_test has %d points" % (int(ys.numel()), m))
+    return n, m, dd
+
+
+def native_batched_mse_value_and_gradient(kernel, X: torch.Tensor, y: torch.Tensor, Xs: torch.Tensor,
+                                          ys: torch.Tensor):
+    """Held-out MSE mean((K_s^T (K + noise I)^-1 y - y_test)^2) and its gradient for a batch of (hyperparameters,
+    noise) candidates by ONE batched factorisation with the test points as extra rows per call (gpk_mse_grad) -- the
+    n^3/3 factorisation, not the identity-augmented n^3 one of the -LML gradient.
+
+    Returns f(cands [B, n_hyp + 1] fp64 on the device, the noise last, settle=False) -> (f [B], g [B, n_hyp + 1],
+    info [B] int32): the contract of :func:`native_batched_value_and_gradient` -- ``.n_par``, candidate rows read in
+    place, enqueue only, ``settle=True`` reads through the factorisation's accessors (a persistent run is then
+    verified and, had it timed out, run again on the launch path).  fp64 only."""
+    as_t = lambda t: t if isinstance(t, torch.Tensor) else torch.as_tensor(t)
+    n, m, d = _check_mse_shapes(as_t(X), as_t(y), as_t(Xs), as_t(ys))
+    X, Xs = engine.as_device_f64(X).contiguous(), engine.as_device_f64(Xs).contiguous()
+    yv = engine.as_device_f64(y).reshape(1, -1).contiguous()
+    ysv = engine.as_device_f64(ys).reshape(1, -1).contiguous()
+    kd = engine.kernel_descriptor(kernel, d)
+    width = kd.n_hyp + 1
+    cache = {}
+
+    def evaluate(cands: torch.Tensor, settle: bool = False):
+        _check_candidates(cands, width, X.device)
+        B = int(cands.shape[0])
+        f = cache.get(B)
+        if f is None:
+            f = cache[B] = engine.AugmentedFactorization(n, d, m, B, torch.float64)
+        flat = cands.reshape(-1)
+        # (the noise operand: the same buffer from element n_hyp on; the last member's noise is its last element)
+        f.run_mse(kd, flat, width, flat[kd.n_hyp:], width, X, 0, yv, 0, Xs, 0, ysv, 0)
+        if settle:
+            return f.mse(), f.mse_grad(), f.info
+        return f.unsettled_mse()
+
+    evaluate.n_par = width
+    return evaluate
+
+
+def native_kfold_mse_value_and_gradient(kernel, folds):
+    """Mean over k folds of the held-out MSE and of its gradient for a batch of (hyperparameters, noise) candidates:
+    the gradient of what CrossValidation(metric_type=MSE) evaluates, as ONE ragged batch of S * F members per call
+    (engine.RaggedFactorization.run_mse_packed -> gpk_mse_grad with n_dev / m_dev).  The folds of
+    Metrics/CrossValidation.get_data_inputs differ in n_train and n_test whenever n is not divisible.
+
+    ``folds``: a list of (X_f [n_f, d], y_f [n_f], Xs_f [m_f >= 1, d], ys_f [m_f]).  Returns f(cands [S, n_hyp + 1],
+    settle=False) -> (f [S], g [S, n_hyp + 1], info [S] int32) as :func:`native_kfold_value_and_gradient`: every fold
+    contributes its own MSE, the folds are reduced in a fixed order (:func:`fold_mean`, :func:`fold_info`); f is +inf
+    and g NaN where any fold's factorisation failed.  Enqueue only (ragged batches never take the persistent launch:
+    ``settle`` has nothing to verify)."""
+    from . import _native as nat
+    if not folds:
+        raise ValueError("at least one fold is needed")
+    as_t = lambda t: t if isinstance(t, torch.Tensor) else torch.as_tensor(t)
+    d, sizes, tsizes = None, [], []
+    for fold in folds:
+        if len(fold) != 4:
+            raise ValueError("every fold is (X, y, X_test, y_test)")
+        nf, mf, d = _check_mse_shapes(*[as_t(t) for t in fold], d=d)
+        sizes.append(nf)
+        tsizes.append(mf)
+    folds = [(engine.as_device_f64(X), engine.as_device_f64(y).reshape(-1), engine.as_device_f64(Xs),
+              engine.as_device_f64(ys).reshape(-1)) for X, y, Xs, ys in folds]
+    F = len(folds)
+    n, m = max(sizes), max(tsizes)
+    dev = folds[0][0].device
+    kd = engine.kernel_descriptor(kernel, d)
+    width = kd.n_hyp + 1
+    Xf = torch.zeros((F, n, d), dtype=torch.float64, device=dev)
+    yf = torch.zeros((F, n), dtype=torch.float64, device=dev)
+    Xsf = torch.zeros((F, m, d), dtype=torch.float64, device=dev)
+    ysf = torch.zeros((F, m), dtype=torch.float64, device=dev)
+    for k, (X, y, Xs, ys) in enumerate(folds):
+        Xf[k, :sizes[k]] = X
+        yf[k, :sizes[k]] = y
+        Xsf[k, :tsizes[k]] = Xs
+        ysf[k, :tsizes[k]] = ys
+    cache = {}
+
+    def evaluate(cands: torch.Tensor, settle: bool = False):
+        _check_candidates(cands, width, dev)
+        S = int(cands.shape[0])
+        slot = cache.get(S)
+        if slot is None:
+            fac = engine.RaggedFactorization(sizes * S, d, tsizes * S, torch.float64)
+            slot = cache[S] = (fac, Xf.repeat(S, 1, 1).contiguous(), yf.repeat(S, 1).contiguous(),
+                               Xsf.repeat(S, 1, 1).contiguous(), ysf.repeat(S, 1).contiguous())
+        fac, Xp, yp, Xsp, ysp = slot
+        hyp, noise = replicate_candidates(cands, F, nat.MAX_HYP)
+        fac.run_mse_packed(kd, hyp, noise, Xp, yp, Xsp, ysp)
+        mse, grad, info = fac.unsettled_mse()
+        return fold_mean(mse, F), fold_mean(grad, F), fold_info(info, F)
+
+    evaluate.n_par = width
+    evaluate.n_folds = F
+    return evaluate
+
+
 class HyperparameterSweep:
     """Evaluate -LML for every row of a candidate matrix across the ranks of ``group``.
 

@@ -279,6 +279,48 @@ int gpk_nlml_grad_ragged(const gpk_kdesc* kd, const gpk_layout* lay, const doubl
                          int32_t* info_dev, double* out_dev, double* grad_dev, void* work, size_t work_bytes,
                          void* stream);
 
+/* Held-out mean squared error and its gradient for every batch member (fp64; entries added without a new ABI number,
+ * found by symbol like gpk_op_supported): the objective of MeanSquaredError.get_metric (Metrics/MeanSquaredError.py:
+ * 26-42) and of CrossValidation's default metric, differentiated as the reference's tape would.  The layout is
+ * planned with m >= 1 test points; W is factored as gpk_assemble + gpk_potrf_aug leave it (test rows V = K_s^T L^-T,
+ * y row z = L^-1 y, -mu in the corner's y row).  With r = mu - ys, alpha = L^-T z and q = L^-T (V^T r):
+ *   mse = r^T r / m,
+ *   d mse / d hyp[p] = (2/m) [ sum_it alpha_i r_t dk(x_i, xs_t)/d hyp[p] - sum_ij q_i alpha_j dk(x_i, x_j)/d hyp[p] ],
+ *   d mse / d noise  = -(2/m) q^T alpha
+ * -- two rank-one weights: no inverse and no n x n cotangent is formed, and the factorisation is the n^3/3 one.
+ *
+ * gpk_mse_grad_workspace_bytes: bytes of `work` for both entries (host only); 0 for a kernel program that is not
+ *   valid for the layout's dimension, or a layout with m < 1.
+ * gpk_mse_backward: the pass alone on an already factored W: one kernel for r, sum r^2 and the right-hand sides
+ *   V^T r and z, the batched backward solve (as gpk_trsv, trans = 1) on both, one tile pass over the lower
+ *   TRAIN x TRAIN and the TEST x TRAIN 64-tiles that re-evaluates the kernel program, and a fixed-order reduction (no
+ *   floating-point atomics: the same inputs give the same bits).  ys[b*ys_bstride + t]: test targets.
+ *   out_dev[b*4 + {0,1,2,3}] = {mse, sum r^2, m_b, n_b}; grad_dev[b*(n_hyp+1) + p] laid out as gpk_nlml_grad's, the
+ *   noise last.  Where info_dev[b] != 0 the mse is +inf and the gradient NaN -- including info = -1, which a
+ *   persistent factorisation sets on the members a timed-out wait left unfinished (gpk_tune "chain_timeout_ms"), as
+ *   in gpk_nlml_grad; the other members are unaffected.
+ *   Ragged batches: n_dev and m_dev both given (device int64 arrays, 1 <= n_dev[b] <= n, 1 <= m_dev[b] <= m: the
+ *   device reads them blindly, the caller checks them) for a W factored by the _ragged entries, or both NULL.  What
+ *   lies in X / Xs / ys past a member's own counts is never read.
+ *   Errors: -1 invalid kernel program, -2 layout invalid or planned with m < 1, -30 layout planned with GPK_F32,
+ *   -3 hyp_dev, -5 X, -7 Xs, -9 ys, -11 only one of n_dev / m_dev, -13 W, -14 Winv, -15 info_dev, -16 out_dev,
+ *   -17 grad_dev, -18 work NULL or too small.
+ * gpk_mse_grad: memset of info + gpk_assemble + gpk_potrf_aug (their _ragged twins when n_dev / m_dev are given) +
+ *   gpk_mse_backward, whose first kernel is the read-out (gpk_finalize is not run: out_dev is the four values above).
+ *   Errors: -1, -2, -30 as above, -3 hyp_dev, -5 noise_dev, -7 X, -9 Xs, -11 y, -13 ys, -15 only one of n_dev / m_dev,
+ *   -17 W, -18 Winv, -19 info_dev, -20 out_dev, -21 grad_dev, -22 work NULL or too small. */
+size_t gpk_mse_grad_workspace_bytes(const gpk_kdesc* kd, const gpk_layout* lay);
+int gpk_mse_backward(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_dev, int64_t hyp_stride,
+                     const double* X, int64_t x_bstride, const double* Xs, int64_t xs_bstride, const double* ys,
+                     int64_t ys_bstride, const int64_t* n_dev, const int64_t* m_dev, const void* W, const void* Winv,
+                     const int32_t* info_dev, double* out_dev, double* grad_dev, void* work, size_t work_bytes,
+                     void* stream);
+int gpk_mse_grad(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_dev, int64_t hyp_stride,
+                 const double* noise_dev, int64_t noise_stride, const double* X, int64_t x_bstride, const double* Xs,
+                 int64_t xs_bstride, const double* y, int64_t y_bstride, const double* ys, int64_t ys_bstride,
+                 const int64_t* n_dev, const int64_t* m_dev, void* W, void* Winv, int32_t* info_dev, double* out_dev,
+                 double* grad_dev, void* work, size_t work_bytes, void* stream);
+
 /* Plain kernel matrix K[i*ldk + j] = k(X_i, Y_j) (+ diag_add where i == j) for i < n, j < m.
  * uplo: 0 = full, 1 = lower triangle only.  dtype selects the stored element type. */
 int gpk_kernel_matrix(const gpk_kdesc* kd, const double* hyp_dev, int dtype, int uplo,

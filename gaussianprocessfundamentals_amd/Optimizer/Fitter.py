@@ -352,3 +352,29 @@ class DeviceKfoldMseLbfgsFitter(DeviceKfoldLbfgsFitter):
         return sweep.native_kfold_mse_value_and_gradient(
             kernel, [(di.data_x_train, di.get_detrended_y_train(), di.data_x_test, di.get_detrended_y_test())
                      for di in self.data_input])
+
+
+class DeviceLooLbfgsFitter(DeviceLbfgsFitter):
+    """:class:`DeviceLbfgsFitter` for the exact leave-one-out objective of a DataInput (Metrics/LeaveOneOut.py):
+    ``metric_type`` LL fits by minus the LOO log predictive density, MSE by the LOO mean squared error.  The loop,
+    starts, bounds and report are the sibling's; every iteration's evaluation is ONE batched identity-augmented
+    factorisation plus the LOO pass (sweep.native_batched_loo_value_and_gradient -> gpk_loo_grad).  Pre- and post-fit
+    metrics are LeaveOneOut.get_metric.  The LOO-MSE is invariant under K -> c K: with a scaled kernel and an optimised
+    noise its minimiser is a ray, compare objective values (or pin the noise)."""
+
+    _METRICS = (met.MetricType.LL, met.MetricType.MSE)
+
+    def __init__(self, data_input, gaussian_process, metric_type: met.MetricType, fitter_type: ft.FitterType,
+                 from_distribution: bool, local_approx: mht.GlobalApproximationsType,
+                 numerical_matrix_handling: mht.NumericalMatrixHandlingType, subset_size: int = None, **kwargs):
+        super().__init__(data_input, gaussian_process, metric_type, fitter_type, from_distribution, local_approx,
+                         numerical_matrix_handling, subset_size, **kwargs)
+        from ..Metrics.LeaveOneOut import LeaveOneOut
+        self.metric = LeaveOneOut(data_input, self._gp.covariance_matrix, local_approx, numerical_matrix_handling,
+                                  subset_size, loss=metric_type)
+
+    def _evaluator(self, kernel):
+        from .. import sweep
+        di = self.data_input
+        return sweep.native_batched_loo_value_and_gradient(kernel, di.data_x_train, di.get_detrended_y_train(),
+                                                           self.metric.loss_code)

@@ -44,12 +44,16 @@ EXPORTS = (
     "gpk_fit_state_bytes", "gpk_fit_init", "gpk_fit_step", "gpk_fit_current",
     "gpk_assemble_inverse_ragged", "gpk_potrf_aug_ragged_ex", "gpk_grad_ragged", "gpk_nlml_grad_ragged",
     "gpk_launch_plan", "gpk_mse_grad_workspace_bytes", "gpk_mse_backward", "gpk_mse_grad",
+    "gpk_loo_workspace_bytes", "gpk_loo_backward", "gpk_loo_grad",
 )
 # the ragged identity-augmented entries (added without a new ABI number, found by symbol)
 RAGGED_GRAD_ENTRIES = ("gpk_assemble_inverse_ragged", "gpk_potrf_aug_ragged_ex", "gpk_grad_ragged",
                        "gpk_nlml_grad_ragged")
 # the held-out MSE and its gradient (likewise)
 MSE_GRAD_ENTRIES = ("gpk_mse_grad_workspace_bytes", "gpk_mse_backward", "gpk_mse_grad")
+# leave-one-out cross-validation (likewise); the losses of include/gpk.h
+LOO_ENTRIES = ("gpk_loo_workspace_bytes", "gpk_loo_backward", "gpk_loo_grad")
+LOO_LPD, LOO_MSE = 0, 1
 
 
 class NativeUnavailable(RuntimeError):
@@ -188,10 +192,15 @@ def _declare(lib):
                                      c_int64, P, P, P, P, P, P, P, P, c_size_t, P]),
         "gpk_mse_grad": (c_int, [POINTER(GpkKdesc), POINTER(GpkLayout), P, c_int64, P, c_int64, P, c_int64, P, c_int64,
                                  P, c_int64, P, c_int64, P, P, P, P, P, P, P, P, c_size_t, P]),
+        "gpk_loo_workspace_bytes": (c_size_t, [POINTER(GpkKdesc), POINTER(GpkLayout)]),
+        "gpk_loo_backward": (c_int, [c_int32, POINTER(GpkKdesc), POINTER(GpkLayout), P, c_int64, P, c_int64, P,
+                                     c_int64, P, P, P, P, P, P, P, P, c_size_t, P]),
+        "gpk_loo_grad": (c_int, [c_int32, POINTER(GpkKdesc), POINTER(GpkLayout), P, c_int64, P, c_int64, P, c_int64, P,
+                                 c_int64, P, P, P, P, P, P, P, P, P, c_size_t, P]),
     }
     for name, (res, args) in sig.items():
         if (name in ("gpk_op_supported", "gpk_launch_plan") or name in RAGGED_GRAD_ENTRIES or
-                name in MSE_GRAD_ENTRIES or
+                name in MSE_GRAD_ENTRIES or name in LOO_ENTRIES or
                 name.startswith(("gpk_mean_", "gpk_fit_"))) and not hasattr(lib, name):
             continue  # (a library built before the entry existed: *op_supported() / fit_supported() then say no)
         fn = getattr(lib, name)
@@ -264,6 +273,32 @@ def require_mse_grad(library=None):
     if not mse_grad_supported(library):
         raise NativeUnavailable("this libgpk.so was built before the held-out MSE entries (gpk_mse_grad and its kin) "
                                 "existed: rebuild it")
+
+
+def loo_supported(library=None) -> bool:
+    """Whether the library has the leave-one-out entries (gpk_loo_workspace_bytes, gpk_loo_backward, gpk_loo_grad;
+    added without a new ABI number); False for one built before they existed -- it still loads, and the engine's loo
+    calls raise NativeUnavailable."""
+    L = library if library is not None else load_library()
+    return all(hasattr(L, n) for n in LOO_ENTRIES)
+
+
+def require_loo(library=None):
+    if not loo_supported(library):
+        raise NativeUnavailable("this libgpk.so was built before the leave-one-out entries (gpk_loo_grad and its kin) "
+                                "existed: rebuild it")
+
+
+def loo_loss_code(loss) -> int:
+    """GPK_LOO_LPD / GPK_LOO_MSE from the code itself or from "lpd" / "mse"."""
+    if isinstance(loss, str):
+        names = {"lpd": LOO_LPD, "ll": LOO_LPD, "mse": LOO_MSE}
+        if loss.lower() not in names:
+            raise ValueError("unknown leave-one-out loss %r (lpd or mse)" % (loss,))
+        return names[loss.lower()]
+    if int(loss) not in (LOO_LPD, LOO_MSE):
+        raise ValueError("unknown leave-one-out loss %r (LOO_LPD or LOO_MSE)" % (loss,))
+    return int(loss)
 
 
 def fit_state_bytes(n_par: int, batch: int, opts: "GpkFitOpts" = None) -> int:

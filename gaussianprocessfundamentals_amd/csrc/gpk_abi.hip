@@ -1234,6 +1234,134 @@ int gpk_mse_grad(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_d
                           Winv, info_dev, out_dev, grad_dev, work, work_bytes, stream);
 }
 
+// ------------------------------------------------------------------------- leave-one-out cross-validation
+// workspace: [batch][4][n_pad] per-point vectors, [batch][slabs][3] partial sums, [batch][n_pad + 1][n_pad] cotangent,
+// [batch][lower tiles][n_hyp + 1] partials of the tile pass
+static size_t loo_pts_elems(const gpk_layout* lay) { return (size_t)lay->batch * 4 * (size_t)lay->n_pad; }
+static size_t loo_slab_elems(const gpk_layout* lay) { return (size_t)lay->batch * 3 * (size_t)loo_slabs(lay->n_pad); }
+static size_t loo_cot_elems(const gpk_layout* lay) {
+  return (size_t)lay->batch * (size_t)(lay->n_pad + 1) * (size_t)lay->n_pad;
+}
+
+size_t gpk_loo_workspace_bytes(const gpk_kdesc* kd, const gpk_layout* lay) {
+  if (!kd || !lay || lay->n <= 0 || lay->m != lay->n || lay->batch <= 0 || lay->dtype != GPK_F64) return 0;
+  if (!valid_kdesc(kd, lay->d)) return 0;  // (gpk_loo_backward refuses such a program: no workspace to size)
+  return (loo_pts_elems(lay) + loo_slab_elems(lay) + loo_cot_elems(lay)) * sizeof(double) +
+         gpk_grad_workspace_bytes(kd, lay);
+}
+
+// the checks the two LOO entries share (argument numbers of loss, kd, lay are theirs in both)
+static int loo_check(int32_t loss, const gpk_kdesc* kd, const gpk_layout* lay) {
+  if (loss != GPK_LOO_LPD && loss != GPK_LOO_MSE) return fail_arg(1, "loss (GPK_LOO_LPD or GPK_LOO_MSE)");
+  if (check_layout(lay)) return fail_arg(3, "layout (use gpk_plan)");
+  if (lay->m != lay->n) return fail_arg(3, "leave-one-out needs a layout planned with m = n");
+  if (lay->dtype != GPK_F64) return fail_arg(30, "leave-one-out is fp64 only (layout planned with GPK_F32)");
+  if (!valid_kdesc(kd, lay->d)) return fail_arg(2, "kernel descriptor");
+  return 0;
+}
+
+int gpk_loo_backward(int32_t loss, const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_dev,
+                     int64_t hyp_stride, const double* X, int64_t x_bstride, const double* y, int64_t y_bstride,
+                     const int64_t* n_dev, const void* W, const int32_t* info_dev, double* out_dev, double* mu_dev,
+                     double* var_dev, double* grad_dev, void* work, size_t work_bytes, void* stream) {
+  if (int e = loo_check(loss, kd, lay)) return e;
+  if (!hyp_dev && kd->n_hyp > 0) return fail_arg(4, "hyp_dev");
+  if (!X) return fail_arg(6, "X");
+  if (!y) return fail_arg(8, "y");
+  if (!W) return fail_arg(11, "W");
+  if (!info_dev) return fail_arg(12, "info_dev");
+  if (!out_dev) return fail_arg(13, "out_dev");
+  if (!work || work_bytes < gpk_loo_workspace_bytes(kd, lay))
+    return fail_arg(17, "work (see gpk_loo_workspace_bytes)");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  LooArgs g;
+  memset(&g, 0, sizeof(g));
+  g.W = static_cast<const double*>(W);
+  g.ld = lay->ld;
+  g.w_bs = lay->w_batch_stride;
+  g.n = lay->n;
+  g.n_pad = lay->n_pad;
+  g.y_row = lay->y_row;
+  g.y = y;
+  g.y_bs = y_bstride;
+  g.loss = loss;
+  g.pts = static_cast<double*>(work);
+  g.slab = g.pts + loo_pts_elems(lay);
+  g.cot = grad_dev ? g.slab + loo_slab_elems(lay) : nullptr;
+  g.out = out_dev;
+  g.mu = mu_dev;
+  g.var = var_dev;
+  g.info = info_dev;
+  g.nb = n_dev;
+  // (timing classes: the read-out 4, the matrix-vector product 5 like gpk_gemv, the cotangent 3 -- the class of the
+  // factorisation's MFMA updates, with its flops -- and the tile pass 6)
+  GPK_HIP(timed(4, 0.0, 0.0, s, [&] { return launch_loo_points(g, lay->batch, s); }), "loo points");
+  if (!grad_dev) return 0;
+  const double nn = (double)lay->n;
+  GPK_HIP(timed(5, 2.0 * nn * nn * lay->batch, 8.0 * 0.5 * nn * nn * lay->batch, s,
+                [&] { return launch_loo_symv(g, lay->batch, s); }),
+          "loo symv");
+  GPK_HIP(timed(3, nn * nn * nn * lay->batch, 0.0, s, [&] { return launch_loo_cot(g, lay->batch, s); }), "loo cot");
+  GradArgs gg;
+  memset(&gg, 0, sizeof(gg));
+  gg.n = lay->n;
+  gg.n_pad = lay->n_pad;
+  gg.y_row = lay->y_row;
+  gg.hyp = hyp_dev;
+  gg.hyp_stride = hyp_stride;
+  gg.X = X;
+  gg.x_bs = x_bstride;
+  gg.d = (int32_t)lay->d;
+  gg.dp = (lay->d % 2 == 0) ? (int32_t)lay->d + 1 : (int32_t)lay->d;
+  gg.ntile = (lay->n + ATILE - 1) / ATILE;
+  gg.part = g.slab + loo_slab_elems(lay) + loo_cot_elems(lay);
+  gg.grad = grad_dev;
+  gg.info = info_dev;
+  gg.nb = n_dev;
+  adjoint_masks(*kd, gg.adj_mask);
+  GPK_HIP(timed(6, 0.0, 0.0, s,
+                [&] {
+                  return launch_grad_cot(*kd, gg, g.cot, lay->n_pad, (lay->n_pad + 1) * lay->n_pad, lay->n_pad,
+                                         lay->batch, s);
+                }),
+          "loo grad");
+  return 0;
+}
+
+int gpk_loo_grad(int32_t loss, const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_dev, int64_t hyp_stride,
+                 const double* noise_dev, int64_t noise_stride, const double* X, int64_t x_bstride, const double* y,
+                 int64_t y_bstride, const int64_t* n_dev, void* W, void* Winv, int32_t* info_dev, double* out_dev,
+                 double* mu_dev, double* var_dev, double* grad_dev, void* work, size_t work_bytes, void* stream) {
+  if (int e = loo_check(loss, kd, lay)) return e;
+  if (!hyp_dev && kd->n_hyp > 0) return fail_arg(4, "hyp_dev");
+  if (!noise_dev) return fail_arg(6, "noise_dev");
+  if (!X) return fail_arg(8, "X");
+  if (!y) return fail_arg(10, "y");
+  if (!W) return fail_arg(13, "W");
+  if (!Winv) return fail_arg(14, "Winv");
+  if (!info_dev) return fail_arg(15, "info_dev");
+  if (!out_dev) return fail_arg(16, "out_dev");
+  if (!work || work_bytes < gpk_loo_workspace_bytes(kd, lay))
+    return fail_arg(20, "work (see gpk_loo_workspace_bytes)");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  GPK_HIP(hipMemsetAsync(info_dev, 0, sizeof(int32_t) * lay->batch, s), "memset info");
+  int e;
+  if (n_dev) {
+    e = gpk_assemble_inverse_ragged(kd, lay, hyp_dev, hyp_stride, noise_dev, noise_stride, X, x_bstride, y, y_bstride,
+                                    n_dev, W, stream);
+    if (e) return e;
+    e = gpk_potrf_aug_ragged_ex(lay, W, Winv, info_dev, GPK_AUG_EXTRA_IDENTITY, n_dev, n_dev, stream);
+  } else {
+    e = gpk_assemble_inverse(kd, lay, hyp_dev, hyp_stride, noise_dev, noise_stride, X, x_bstride, y, y_bstride, W,
+                             stream);
+    if (e) return e;
+    e = gpk_potrf_aug_ex(lay, W, Winv, info_dev, GPK_AUG_EXTRA_IDENTITY, stream);
+  }
+  if (e) return e;
+  return gpk_loo_backward(loss, kd, lay, hyp_dev, hyp_stride, X, x_bstride, y, y_bstride, n_dev, W, info_dev, out_dev,
+                          mu_dev, var_dev, grad_dev, work, work_bytes, stream);
+}
+
 int gpk_kernel_matrix(const gpk_kdesc* kd, const double* hyp_dev, int dtype, int uplo,
                       const double* X, int64_t n, const double* Y, int64_t m, int32_t d,
                       double diag_add, void* K, int64_t ldk, void* stream) {

@@ -1,7 +1,8 @@
 // Reverse mode of the kernel program: the LML gradient (gpk_nlml_grad: grad_kernel), the adjoints of a rectangular
 // kernel matrix (gpk_kernel_vjp: vjp_kernel) and the gradient of the held-out mean squared error (gpk_mse_backward:
 // mse_tile_kernel).  All walk 64 x 64 tiles staged as the K build stages them (gpk_stage.h) and re-evaluate the
-// program per element with the reference's literal formulas (base_values, gpk_kernels.h).
+// program per element with the reference's literal formulas (base_values, gpk_kernels.h).  launch_grad_cot runs
+// grad_kernel over a cotangent buffer instead of W's corner (the leave-one-out gradient, gpk_loo.hip): a host launcher.
 // Two things are written more than once here on purpose, in the same words, and a change to one belongs in the others
 // (profiles/grad_split_codegen.txt, profiles/grad_split_ab.txt):
 // - the three kernels' loops over the program's leaves (adjoint product over adj_mask, base_partials, the leaf's
@@ -961,6 +962,53 @@ hipError_t launch_grad(const gpk_kdesc& kd, const GradArgs& g, int dtype, int32_
     if (e != hipSuccess) return e;
   }
   hipLaunchKernelGGL(grad, grid, dim3(256), lds, s, kd, a, g);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)(kd.n_hyp + 1), (unsigned)batch), dim3(256), 0, s,
+                     g, ntri, kd.n_hyp + 1);
+  return hipGetLastError();
+}
+
+// launch_grad with the weights read from a cotangent buffer (gpk_loo_backward): the AsmArgs that stage_points reads
+// carry g0's real layout, the GradArgs fields that address the corner and its y row (g.W, g.ld, g.w_bs, g.n_pad,
+// g.y_row: grad_kernel uses them for nothing else) carry the buffer's.  The kernels are launch_grad's f64 ones.
+hipError_t launch_grad_cot(const gpk_kdesc& kd, const GradArgs& g0, const double* C, int64_t c_ld, int64_t c_bs,
+                           int64_t c_yrow, int32_t batch, hipStream_t s) {
+  AsmArgs a;
+  memset(&a, 0, sizeof(a));
+  a.hyp = g0.hyp;
+  a.hyp_stride = g0.hyp_stride;
+  a.X = g0.X;
+  a.x_bs = g0.x_bs;
+  a.n = g0.n;
+  a.m = g0.n;
+  a.n_pad = g0.n_pad;
+  a.y_row = g0.y_row;
+  a.d = g0.d;
+  a.dp = g0.dp;
+  a.eye = 1;
+  a.nb = g0.nb;
+  a.mb = g0.nb;
+  GradArgs g = g0;
+  g.W = C;
+  g.ld = c_ld;
+  g.w_bs = c_bs;
+  g.n_pad = 0;
+  g.y_row = c_yrow;
+  const int64_t ntri = g.ntile * (g.ntile + 1) / 2;
+  bool has_mul = false;
+  for (int q = 0; q < kd.n_nodes; ++q) has_mul |= g.adj_mask[q] != 0u;
+  const size_t lds = sizeof(double) * (GPK_MAX_HYP + 2 * ATILE + 4 * (GNP + 1) +
+                                       2 * (size_t)(1 + kd.n_ard) * ATILE * a.dp +
+                                       (has_mul ? (size_t)kd.n_nodes * 256 : 0));
+  const bool rq = rq_leaves(kd) > 0;
+  const auto grad = g.nb != nullptr ? (rq ? grad_kernel<double, true, true> : grad_kernel<double, false, true>)
+                                    : (rq ? grad_kernel<double, true> : grad_kernel<double, false>);
+  {
+    hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(grad), lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(grad, dim3((unsigned)ntri, (unsigned)batch, 1), dim3(256), lds, s, kd, a, g);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)(kd.n_hyp + 1), (unsigned)batch), dim3(256), 0, s,

@@ -264,6 +264,25 @@ struct MseArgs {
   const int64_t* mb;
 };
 
+// gpk_loo_backward (gpk_loo.hip): leave-one-out read-out and cotangent of a factored identity-augmented W (fp64)
+struct LooArgs {
+  const double* W;     // corner -K^-1 (lower triangle), the corner's y row -alpha^T
+  int64_t ld;
+  int64_t w_bs;
+  int64_t n, n_pad, y_row;
+  const double* y;     // the assembled targets
+  int64_t y_bs;
+  int32_t loss;        // GPK_LOO_LPD / GPK_LOO_MSE
+  double* pts;         // [batch][4][n_pad]: phi_alpha, phi_d, alpha, u (zeros at and past the member's n_b)
+  double* slab;        // [batch][loo_slabs(n_pad)][3] partial sums of f, (alpha / d)^2, log(1 / d)
+  double* cot;         // [batch][n_pad + 1][n_pad] cotangent C = -2 G (lower triangle), last row zeros; NULL: value only
+  double* out;         // [batch][4]: f, sum (alpha / d)^2, sum log sigma^2, n_b
+  double* mu;          // [batch][n] (may be NULL)
+  double* var;
+  const int32_t* info;
+  const int64_t* nb;   // ragged batches: training points of member b (NULL: n)
+};
+
 // gpk_kernel_vjp (gpk_grad.hip): adjoints of K(X, Z) = kernel(X, Z) for a weight matrix G [n, ldg]
 struct VjpArgs {
   const double* hyp;   // [n_hyp] device
@@ -304,6 +323,15 @@ hipError_t launch_finalize(const FinArgs& a, int dtype, int32_t batch, hipStream
 hipError_t launch_chain(const ChainArgs& a, int dtype, int grid, hipStream_t s);
 hipError_t chain_timeouts_read(int64_t* out);  // timed-out persistent launches on this device (synchronous)
 hipError_t launch_grad(const gpk_kdesc& kd, const GradArgs& g, int dtype, int32_t batch, hipStream_t s);
+// grad_kernel / grad_reduce_kernel over a cotangent buffer C [batch][c_rows][c_ld] instead of W's corner: the points are
+// staged through g's real layout, the weight -C_ij - a_i a_j is read with the corner at (0, 0) and the "y row" a at row
+// c_yrow of C (gpk_loo_backward: a row of zeros).  fp64.
+hipError_t launch_grad_cot(const gpk_kdesc& kd, const GradArgs& g, const double* C, int64_t c_ld, int64_t c_bs,
+                           int64_t c_yrow, int32_t batch, hipStream_t s);
+int64_t loo_slabs(int64_t n_pad);  // workgroups per member of the LOO read-out
+hipError_t launch_loo_points(const LooArgs& g, int32_t batch, hipStream_t s);
+hipError_t launch_loo_symv(const LooArgs& g, int32_t batch, hipStream_t s);
+hipError_t launch_loo_cot(const LooArgs& g, int32_t batch, hipStream_t s);
 int64_t mse_tiles(int64_t n, int64_t m);  // tiles of the MSE gradient's tile pass
 hipError_t launch_mse_residual(const MseArgs& g, int32_t batch, hipStream_t s);
 hipError_t launch_mse_tiles(const gpk_kdesc& kd, const MseArgs& g, int32_t batch, hipStream_t s);

@@ -711,9 +711,96 @@ class InverseFactorization(AugmentedFactorization):
                                   nat.ptr(noise), noise_stride, nat.ptr(X), x_bstride, nat.ptr(y), y_bstride,
                                   nat.ptr(self.W), nat.ptr(self.Winv), nat.ptr(self.info), nat.ptr(self.out),
                                   grad_ptr, work_ptr, work_bytes, nat.stream_handle(dev)), "gpk_nlml_grad")
+        self._loo_operands = (kd, hyp, hyp_stride, X, x_bstride, y, y_bstride)   # (what loo() needs of this run)
         self.kd = kd
         self.done = True
         return self
+
+    # -- leave-one-out cross-validation (gpk_loo_backward / gpk_loo_grad) ------------------------
+    def _loo_buffers(self, kd, gradient: bool):
+        """The workspace is kept between calls; the result buffers (out [B * 4], mu and var [B, n], grad
+        [B, n_hyp + 1]) are the caching allocator's per evaluation, so earlier views stay valid (as _fresh_out)."""
+        nat.require_loo(self.L)
+        if self.code != nat.GPK_F64:
+            raise NotImplementedError("leave-one-out is fp64 only")
+        dev = self._W.device
+        need = int(self.L.gpk_loo_workspace_bytes(ctypes.byref(kd), ctypes.byref(self.layout)))
+        if need == 0:
+            raise ValueError("the kernel program is not valid for dimension %d" % self.d)
+        if getattr(self, "_loo_work", None) is None or self._loo_work.numel() * 8 < need:
+            self._loo_work = torch.empty(need // 8, dtype=torch.float64, device=dev)
+        self._loo_out = torch.empty(self.batch * 4, dtype=torch.float64, device=dev)
+        self._loo_mu = torch.empty((self.batch, self.n), dtype=torch.float64, device=dev)
+        self._loo_var = torch.empty((self.batch, self.n), dtype=torch.float64, device=dev)
+        self._loo_grad = (torch.empty((self.batch, kd.n_hyp + 1), dtype=torch.float64, device=dev)
+                          if gradient else None)
+        return self._loo_work
+
+    def loo(self, loss, gradient: bool = True):
+        """The leave-one-out pass alone on the last :meth:`run` (gpk_loo_backward; W is only read):
+        (f [B], grad [B, n_hyp + 1] or None, mu [B, n], var [B, n]) device views, enqueued without a host
+        synchronisation (a pending persistent run is settled first, like every read of W).  ``loss``:
+        nat.LOO_LPD (minus the LOO log predictive density) or nat.LOO_MSE; f is +inf, the rest NaN where info != 0.
+        mu is in the units of the y that was factored."""
+        ops = getattr(self, "_loo_operands", None) if self.done else None
+        if ops is None:
+            raise RuntimeError("run(...) first")
+        loss = nat.loo_loss_code(loss)
+        kd, hyp, hyp_stride, X, x_bstride, y, y_bstride = ops
+        work = self._loo_buffers(kd, gradient)
+        dev = self._W.device
+        nat.check(self.L.gpk_loo_backward(
+            loss, ctypes.byref(kd), ctypes.byref(self.layout), nat.ptr(hyp), hyp_stride, nat.ptr(X), x_bstride,
+            nat.ptr(y), y_bstride, None, nat.ptr(self.W), nat.ptr(self.info), nat.ptr(self._loo_out),
+            nat.ptr(self._loo_mu), nat.ptr(self._loo_var), nat.ptr(self._loo_grad), nat.ptr(work), work.numel() * 8,
+            nat.stream_handle(dev)), "gpk_loo_backward")
+        return self._loo_out.view(self.batch, 4)[:, 0], self._loo_grad, self._loo_mu, self._loo_var
+
+    def run_loo(self, loss, kd: nat.GpkKdesc, hyp: torch.Tensor, hyp_stride: int, noise: torch.Tensor,
+                noise_stride: int, X: torch.Tensor, x_bstride: int, y: torch.Tensor, y_bstride: int,
+                gradient: bool = True):
+        """K build + identity-augmented factorisation + the leave-one-out pass as one call (gpk_loo_grad);
+        asynchronous, a persistent run is verified at the first read (:meth:`loo_results`, info).
+        ``unsettled_loo()`` gives the views without that."""
+        args = (nat.loo_loss_code(loss), kd, hyp, hyp_stride, noise, noise_stride, X, x_bstride, y, y_bstride,
+                gradient)
+        self._pending = None
+        self._run_loo_once(*args)
+        self._defer_verify(lambda: self._run_loo_once(*args))
+        return self
+
+    def _run_loo_once(self, loss, kd, hyp, hyp_stride, noise, noise_stride, X, x_bstride, y, y_bstride, gradient):
+        B, n, d = self.batch, self.n, self.d
+        dev = self._W.device
+        self._alphas = None
+        self.grad = None
+        work = self._loo_buffers(kd, gradient)
+        _check_operand("hyper_parameter", hyp, hyp_stride, kd.n_hyp, B, dev)
+        _check_operand("noise", noise, noise_stride, 1, B, dev)
+        _check_operand("X", X, x_bstride, n * d, B, dev)
+        _check_operand("y", y, y_bstride, n, B, dev)
+        nat.check(self.L.gpk_loo_grad(
+            loss, ctypes.byref(kd), ctypes.byref(self.layout), nat.ptr(hyp), hyp_stride, nat.ptr(noise), noise_stride,
+            nat.ptr(X), x_bstride, nat.ptr(y), y_bstride, None, nat.ptr(self._W), nat.ptr(self._Winv),
+            nat.ptr(self._info), nat.ptr(self._loo_out), nat.ptr(self._loo_mu), nat.ptr(self._loo_var),
+            nat.ptr(self._loo_grad), nat.ptr(work), work.numel() * 8, nat.stream_handle(dev)), "gpk_loo_grad")
+        self._loo_operands = (kd, hyp, hyp_stride, X, x_bstride, y, y_bstride)
+        self._keep_loo = noise
+        self.kd = kd
+        self.done = True
+        return self
+
+    def loo_results(self):
+        """(f [B], grad [B, n_hyp + 1] or None, mu [B, n], var [B, n]) of the last run_loo / loo (settles a pending
+        persistent run)."""
+        self._settle()
+        if getattr(self, "_loo_out", None) is None:
+            raise RuntimeError("run_loo(...) or loo(...) first")
+        return self._loo_out.view(self.batch, 4)[:, 0], self._loo_grad, self._loo_mu, self._loo_var
+
+    def unsettled_loo(self):
+        """(f, gradient, info) device views WITHOUT settling a pending persistent run (see unsettled_results)."""
+        return self._loo_out.view(self.batch, 4)[:, 0], self._loo_grad, self._info
 
     def gradient(self) -> torch.Tensor:
         """[batch, n_hyp + 1] fp64: d(-LML)/d hyp (DFS order), then d(-LML)/d noise."""
@@ -1041,6 +1128,49 @@ class RaggedInverseFactorization(AugmentedFactorization):
         self.kd = list(kds)
         self.done = True
         return self
+
+    # -- leave-one-out cross-validation (gpk_loo_backward with n_dev) ----------------------------
+    def loo(self, loss, gradient: bool = True):
+        """The leave-one-out pass alone on the last :meth:`run` for every member (gpk_loo_backward with the members'
+        sizes; W is only read): (f [B], grads, mu [B, n], var [B, n]) device views, enqueued without a host
+        synchronisation.  ``grads``: None without ``gradient``, else a list with member b's [n_hyp_b + 1] gradient
+        (noise last).  mu / var are zero past a member's size; f is +inf, the rest NaN where info[b] != 0.  The
+        workspace is kept between calls; the result buffers are the caching allocator's per evaluation."""
+        if not self.done:
+            raise RuntimeError("run(...) first")
+        nat.require_loo(self.L)
+        if self.code != nat.GPK_F64:
+            raise NotImplementedError("leave-one-out is fp64 only")
+        loss = nat.loo_loss_code(loss)
+        X, y, hyp, _ = self._keep
+        kds = self.kd
+        B, n, d = self.batch, self.n, self.d
+        L, lay, dev = self.L, self.layout, self._W.device
+        s = nat.stream_handle(dev)
+        runs = program_runs(kds)
+        lays = {b1 - b0: (lay if b1 - b0 == B else nat.plan(self.code, b1 - b0, n, n, d)) for b0, b1 in runs}
+        need = max(int(L.gpk_loo_workspace_bytes(ctypes.byref(kds[b0]), ctypes.byref(lays[b1 - b0])))
+                   for b0, b1 in runs)
+        if need == 0:
+            raise ValueError("the kernel program is not valid for dimension %d" % d)
+        if getattr(self, "_loo_work", None) is None or self._loo_work.numel() * 8 < need:
+            self._loo_work = torch.empty(need // 8, dtype=torch.float64, device=dev)
+        out = torch.empty(B * 4, dtype=torch.float64, device=dev)
+        mu = torch.empty((B, n), dtype=torch.float64, device=dev)
+        var = torch.empty((B, n), dtype=torch.float64, device=dev)
+        grads = [] if gradient else None
+        for b0, b1 in runs:
+            kd, sl = kds[b0], lays[b1 - b0]
+            g = torch.empty((b1 - b0, kd.n_hyp + 1), dtype=torch.float64, device=dev) if gradient else None
+            nat.check(L.gpk_loo_backward(
+                loss, ctypes.byref(kd), ctypes.byref(sl), _offset_ptr(hyp, b0 * nat.MAX_HYP), nat.MAX_HYP,
+                _offset_ptr(X, b0 * n * d), n * d, _offset_ptr(y, b0 * n), n, _offset_ptr(self.n_dev, b0),
+                _offset_ptr(self._W, b0 * lay.w_batch_stride), _offset_ptr(self._info, b0), _offset_ptr(out, b0 * 4),
+                _offset_ptr(mu, b0 * n), _offset_ptr(var, b0 * n), nat.ptr(g), nat.ptr(self._loo_work),
+                self._loo_work.numel() * 8, s), "gpk_loo_backward")
+            if gradient:
+                grads.extend(g[k] for k in range(b1 - b0))
+        return out.view(B, 4)[:, 0], grads, mu, var
 
     # -- per-member read-out (device views, no host synchronisation) ---------------------------
     def gradients(self) -> torch.Tensor:

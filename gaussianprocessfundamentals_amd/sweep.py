@@ -293,6 +293,50 @@ def native_batched_mse_value_and_gradient(kernel, X: torch.Tensor, y: torch.Tens
     return evaluate
 
 
+def native_batched_loo_value_and_gradient(kernel, X: torch.Tensor, y: torch.Tensor, loss, dtype=None):
+    """Leave-one-out objective (``loss``: _native.LOO_LPD, minus the LOO log predictive density, or _native.LOO_MSE)
+    and its gradient for a batch of (hyperparameters, noise) candidates by ONE batched identity-augmented factorisation
+    plus the LOO pass per call (gpk_loo_grad) -- the factorisation of the -LML gradient, then one n^3 product for the
+    cotangent.
+
+    Returns f(cands [B, n_hyp + 1] fp64 on the device, the noise last, settle=False) -> (f [B], g [B, n_hyp + 1],
+    info [B] int32): the contract of :func:`native_batched_value_and_gradient` -- ``.n_par``, candidate rows read in
+    place, enqueue only, ``settle=True`` reads through the factorisation's accessors (a persistent run is then
+    verified and, had it timed out, run again on the launch path).  fp64 only (``dtype``: None or torch.float64)."""
+    from . import _native as nat
+    if dtype not in (None, torch.float64):
+        raise NotImplementedError("leave-one-out is fp64 only")
+    code = nat.loo_loss_code(loss)
+    as_t = lambda t: t if isinstance(t, torch.Tensor) else torch.as_tensor(t)
+    if as_t(X).dim() != 2 or int(as_t(X).shape[0]) < 1:
+        raise ValueError("X must be [n >= 1, d]")
+    n, d = int(as_t(X).shape[0]), int(as_t(X).shape[1])
+    if int(as_t(y).numel()) != n:
+        raise ValueError("y has %d values, X has %d points" % (int(as_t(y).numel()), n))
+    X = engine.as_device_f64(X).contiguous()
+    yv = engine.as_device_f64(y).reshape(1, -1).contiguous()
+    kd = engine.kernel_descriptor(kernel, d)
+    width = kd.n_hyp + 1
+    cache = {}
+
+    def evaluate(cands: torch.Tensor, settle: bool = False):
+        _check_candidates(cands, width, X.device)
+        B = int(cands.shape[0])
+        f = cache.get(B)
+        if f is None:
+            f = cache[B] = engine.InverseFactorization(n, d, B, torch.float64)
+        flat = cands.reshape(-1)
+        # (the noise operand: the same buffer from element n_hyp on; the last member's noise is its last element)
+        f.run_loo(code, kd, flat, width, flat[kd.n_hyp:], width, X, 0, yv, 0, gradient=True)
+        if settle:
+            v, g, _, _ = f.loo_results()
+            return v, g, f.info
+        return f.unsettled_loo()
+
+    evaluate.n_par = width
+    return evaluate
+
+
 def native_kfold_mse_value_and_gradient(kernel, folds):
     """Mean over k folds of the held-out MSE and of its gradient for a batch of (hyperparameters, noise) candidates:
     the gradient of what CrossValidation(metric_type=MSE) evaluates, as ONE ragged batch of S * F members per call

@@ -321,6 +321,52 @@ int gpk_mse_grad(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_d
                  const int64_t* n_dev, const int64_t* m_dev, void* W, void* Winv, int32_t* info_dev, double* out_dev,
                  double* grad_dev, void* work, size_t work_bytes, void* stream);
 
+/* Leave-one-out cross-validation for every batch member (fp64; entries added without a new ABI number, found by symbol
+ * like gpk_op_supported): Rasmussen & Williams 5.4.2.  The layout is planned with m = n and W factored as
+ * gpk_assemble_inverse + gpk_potrf_aug_ex(GPK_AUG_EXTRA_IDENTITY) leave it (corner -K^-1, the corner's y row -alpha^T).
+ * With d_i = (K^-1)_ii the prediction of point i from the other n - 1 points is
+ *   mu_i = y_i - alpha_i / d_i,  sigma_i^2 = 1 / d_i   (d_i > 0 wherever info == 0),
+ * so all n refits are an O(n) read-out.  loss selects f = sum_i phi(alpha_i, d_i):
+ *   GPK_LOO_LPD  minus the LOO log predictive density (minus R&W eq. 5.13, summed like -LML):
+ *                phi = 1/2 log 2 pi - 1/2 log d + alpha^2 / (2 d)
+ *   GPK_LOO_MSE  the LOO mean squared error: phi = (alpha / d)^2 / n
+ * and the gradient follows from d alpha = -K^-1 dK alpha, d d_i = -(K^-1 dK K^-1)_ii:
+ *   d f / d K = G = -1/2 (alpha u^T + u alpha^T) - K^-1 diag(phi_d) K^-1,  u = K^-1 phi_alpha,
+ *   d f / d hyp[p] = sum_ij G_ij dK_ij / d hyp[p],  d f / d noise = tr G
+ * -- one n^3 product on the f64 matrix cores (lower tiles only) for the whole cotangent, then the tile pass of
+ * gpk_nlml_grad over it.  Fixed-order sums, no floating-point atomics: the same inputs give the same bits.  W is only
+ * read.
+ *
+ * gpk_loo_workspace_bytes: bytes of `work` for both entries (host only); 0 for an invalid kernel program, a layout
+ *   planned with m != n or with GPK_F32.
+ * gpk_loo_backward: the pass alone on a W factored by gpk_nlml_grad (or gpk_nlml_grad_ragged) with any grad_dev.
+ *   y[b*y_bstride + i]: the targets that were assembled (detrended ones when a mean function was subtracted); mu is in
+ *   those units.  out_dev[b*4 + {0,1,2,3}] = {f, sum_i (alpha_i / d_i)^2, sum_i log sigma_i^2, n_b};
+ *   mu_dev[b*n + i], var_dev[b*n + i]: the LOO predictions (either may be NULL; zeros past a ragged member's n_b);
+ *   grad_dev[b*(n_hyp+1) + p] laid out as gpk_nlml_grad's, the noise last.  grad_dev == NULL: value and predictions
+ *   only (the read-out kernels alone).  Where info_dev[b] != 0 f is +inf, the gradient and the predictions NaN --
+ *   including info = -1 of a timed-out persistent factorisation; the other members are unaffected.
+ *   Ragged batches: n_dev (device int64, 1 <= n_dev[b] <= n, read blindly) for a W factored by the _ragged entries,
+ *   or NULL.  What lies in X / y past a member's own count is never read, nor is any element of the corner there.
+ *   Errors: -1 unknown loss, -2 invalid kernel program, -3 layout invalid or planned with m != n, -30 layout planned
+ *   with GPK_F32, -4 hyp_dev, -6 X, -8 y, -11 W, -12 info_dev, -13 out_dev, -17 work NULL or too small.
+ * gpk_loo_grad: memset of info + gpk_assemble_inverse + gpk_potrf_aug_ex(GPK_AUG_EXTRA_IDENTITY) (their _ragged twins
+ *   when n_dev is given) + gpk_loo_backward (gpk_finalize is not run: out_dev is the four values above).
+ *   Errors: -1, -2, -3, -30 as above, -4 hyp_dev, -6 noise_dev, -8 X, -10 y, -13 W, -14 Winv, -15 info_dev,
+ *   -16 out_dev, -20 work NULL or too small.
+ * Every argument check precedes any device work.  gpk_timing_read classes of the pass: 4 the read-out, 5 u, 3 the
+ * cotangent product (with its n^3 flops per member), 6 the tile pass. */
+enum { GPK_LOO_LPD = 0, GPK_LOO_MSE = 1 };
+size_t gpk_loo_workspace_bytes(const gpk_kdesc* kd, const gpk_layout* lay);
+int gpk_loo_backward(int32_t loss, const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_dev,
+                     int64_t hyp_stride, const double* X, int64_t x_bstride, const double* y, int64_t y_bstride,
+                     const int64_t* n_dev, const void* W, const int32_t* info_dev, double* out_dev, double* mu_dev,
+                     double* var_dev, double* grad_dev, void* work, size_t work_bytes, void* stream);
+int gpk_loo_grad(int32_t loss, const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_dev, int64_t hyp_stride,
+                 const double* noise_dev, int64_t noise_stride, const double* X, int64_t x_bstride, const double* y,
+                 int64_t y_bstride, const int64_t* n_dev, void* W, void* Winv, int32_t* info_dev, double* out_dev,
+                 double* mu_dev, double* var_dev, double* grad_dev, void* work, size_t work_bytes, void* stream);
+
 /* Plain kernel matrix K[i*ldk + j] = k(X_i, Y_j) (+ diag_add where i == j) for i < n, j < m.
  * uplo: 0 = full, 1 = lower triangle only.  dtype selects the stored element type. */
 int gpk_kernel_matrix(const gpk_kdesc* kd, const double* hyp_dev, int dtype, int uplo,

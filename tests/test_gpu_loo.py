@@ -1,0 +1,290 @@
+"""Leave-one-out cross-validation on the HIP path (gpk_loo_grad / gpk_loo_backward) against the restatement of
+tests/loo_support.py (needs the MI355X).
+
+Value: rel <= 1e-8 against torch on the CPU.  Gradient: |g - g_ref| <= 1e-7 max(1, |g_ref|_max) against reverse mode
+through the whole expression.  Predictions: |mu - mu_ref| <= 1e-8 max(1, |mu_ref|_max), the same for the variances.
+Sizes 1, 2, 64, 97, 130: a single element, two, one exact tile, a ragged second tile, three tiles past one panel
+width.  Every comparison is against the restatement, never against the code under test.
+"""
+import functools
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import gaussianprocessfundamentals_amd.global_parameters as gp
+from gaussianprocessfundamentals_amd import _native as nat
+from gaussianprocessfundamentals_amd import engine, sweep
+from gaussianprocessfundamentals_amd.DataHandling.DataInput import DataInput
+from gaussianprocessfundamentals_amd.MeanFunctionBasics.BaseMeanFunctions import LinearMeanFunction, ZeroMeanFunction
+from gaussianprocessfundamentals_amd.Metrics import MatrixHandlingTypes as mht
+from gaussianprocessfundamentals_amd.Metrics.LeaveOneOut import LeaveOneOut
+from gaussianprocessfundamentals_amd.Metrics.Metrics import MetricType
+from gaussianprocessfundamentals_amd.Statistics.GaussianProcess import GaussianProcess
+from tests import loo_support as ls
+from tests import rq_support
+from tests.helpers import hyp_list, make_kernel, set_flags
+
+pytestmark = pytest.mark.gpu
+
+SE, PER, RQ = ls.SE, ls.PER, ("RQ", {})
+SE_PER = ("ADD", [SE, PER])
+SIZES = (1, 2, 64, 97, 130)
+# name: (tree, three candidates' hyperparameters, their noises (>= 1e-2), d)
+PROGRAMS = {
+    "SE": (SE, [[0.3], [0.2], [0.45]], [0.05, 0.01, 0.1], 1),
+    "ADD_SE_PER": (SE_PER, [[0.3, 0.9, 0.5], [0.2, 0.7, 0.4], [0.5, 1.2, 0.8]], [0.05, 0.02, 0.1], 1),
+    "RQ": (RQ, [[0.3, 1.5], [0.2, 0.8], [0.4, 3.0]], [0.05, 0.01, 0.1], 1),
+    "SE_ard_d3": (("SE", {"ard": True}), [[[0.4, 0.7, 1.1]], [[0.6, 0.5, 0.9]], [[0.8, 1.0, 0.6]]], [0.05, 0.02, 0.1], 3),
+}
+CASES = [(name, n) for name in ("SE", "ADD_SE_PER", "RQ") for n in SIZES] + [("SE_ard_d3", 97)]
+LOSSES = [ls.LPD, ls.MSE]
+
+
+@pytest.fixture(autouse=True)
+def _flags():
+    gp.init(0)
+    set_flags()
+    yield
+    set_flags()
+
+
+def _dev(a):
+    return torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=engine.device())
+
+
+def _kernel(tree, d):
+    return rq_support.make_kernel(tree, d) if ls.ms.has_op(tree, "RQ") else make_kernel(tree, d)
+
+
+@functools.lru_cache(maxsize=None)
+def _data(name, n):
+    return ls.inputs(n, PROGRAMS[name][3], 100 + n)
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(name, n, loss, b):
+    """(f, g, mu, var) of candidate b, computed once and shared (read-only)."""
+    tree, hyps, noises, _ = PROGRAMS[name]
+    x, y = _data(name, n)
+    return ls.loo_autodiff(tree, hyps[b], noises[b], x, y, loss)
+
+
+def _candidates(name):
+    _, hyps, noises, _ = PROGRAMS[name]
+    return np.array([np.concatenate([ls.flat(h), [nz]]) for h, nz in zip(hyps, noises)])
+
+
+def _factor(name, n, cands=None, gradient=False):
+    """The batch of three candidates factored by gpk_nlml_grad (InverseFactorization.run)."""
+    tree, _, _, d = PROGRAMS[name]
+    x, y = _data(name, n)
+    kd = engine.kernel_descriptor(_kernel(tree, d), d)
+    C = _dev(_candidates(name) if cands is None else cands)
+    width = kd.n_hyp + 1
+    assert C.shape[1] == width
+    f = engine.InverseFactorization(n, d, C.shape[0], torch.float64)
+    flat = C.reshape(-1)
+    f.run(kd, flat, width, flat[kd.n_hyp:], width, _dev(x), 0, _dev(y).reshape(1, -1), 0, gradient=gradient)
+    f._keep_test = C
+    return f
+
+
+@pytest.mark.parametrize("loss", LOSSES)
+@pytest.mark.parametrize("name,n", CASES)
+def test_value_gradient_and_predictions(name, n, loss):
+    """Three candidates with their own hyperparameters and noises in one batch, each against its own reference."""
+    fac = _factor(name, n)
+    f, g, mu, var = fac.loo(loss, gradient=True)
+    assert not fac.info.cpu().numpy().any()
+    f, g, mu, var = f.cpu().numpy(), g.cpu().numpy(), mu.cpu().numpy(), var.cpu().numpy()
+    out = fac._loo_out.view(-1, 4).cpu().numpy()
+    for b in range(3):
+        f_ref, g_ref, mu_ref, var_ref = _reference(name, n, loss, b)
+        ls.assert_value_close(float(f[b]), f_ref, "%s n=%d b=%d" % (name, n, b))
+        ls.assert_grad_close(g[b], g_ref, "%s n=%d b=%d" % (name, n, b))
+        ls.assert_pred_close(mu[b], mu_ref, "mu")
+        ls.assert_pred_close(var[b], var_ref, "var")
+        # out[1], out[2]: sum (alpha / d)^2 = sum (y - mu)^2 and sum log sigma^2, out[3] = n
+        y = _data(name, n)[1]
+        r2, lv = float(np.sum((y - mu_ref) ** 2)), float(np.sum(np.log(var_ref)))
+        assert abs(out[b, 1] - r2) <= ls.VALUE_REL * r2
+        assert abs(out[b, 2] - lv) <= ls.VALUE_REL * max(1.0, abs(lv))
+        assert out[b, 3] == n
+    # the value-only call (no cotangent, no tile pass): the same value and predictions, bit for bit
+    f2, g2, mu2, var2 = fac.loo(loss, gradient=False)
+    assert g2 is None
+    assert np.array_equal(f2.cpu().numpy(), f) and np.array_equal(mu2.cpu().numpy(), mu)
+    assert np.array_equal(var2.cpu().numpy(), var)
+
+
+def test_known_answer_at_one_point():
+    """n = 1: mu = 0, sigma^2 = k(x, x) + noise, f_LPD = -LML (the same factorisation's read-out)."""
+    fac = _factor("SE", 1)
+    nl = fac.nlml().cpu().numpy().copy()
+    f, _, mu, var = fac.loo(ls.LPD, gradient=False)
+    noises = np.array(PROGRAMS["SE"][2])
+    ls.assert_pred_close(mu.cpu().numpy().reshape(-1), np.zeros(3), "mu")   # (y - (y d) / d: zero to rounding, not exactly)
+    assert np.max(np.abs(var.cpu().numpy().reshape(-1) - (1.0 + noises))) <= 1e-15
+    assert np.max(np.abs(f.cpu().numpy() - nl)) <= 1e-14 * np.max(np.abs(nl))
+
+
+@pytest.mark.parametrize("loss", LOSSES)
+def test_determinism_and_w_intact(loss):
+    """Two calls on the same inputs give the same bits; K^-1, alpha and -LML read after the pass are bitwise what they
+    were before it."""
+    fac = _factor("ADD_SE_PER", 130)
+    before = [(fac.k_inv(b).clone(), fac.alpha(b).clone()) for b in range(3)]
+    nl, w = fac.nlml().clone(), fac.W.clone()
+    a = [t.clone() for t in fac.loo(loss)]
+    b = [t.clone() for t in fac.loo(loss)]
+    for u, v in zip(a, b):
+        assert torch.equal(u, v)
+    assert torch.equal(fac.W, w) and torch.equal(fac.nlml(), nl)
+    for k in range(3):
+        assert torch.equal(fac.k_inv(k), before[k][0]) and torch.equal(fac.alpha(k), before[k][1])
+    # the composite (gpk_loo_grad) on a fresh object: the pass's bits
+    tree, _, _, d = PROGRAMS["ADD_SE_PER"]
+    x, y = _data("ADD_SE_PER", 130)
+    kd = engine.kernel_descriptor(_kernel(tree, d), d)
+    C = _dev(_candidates("ADD_SE_PER")).reshape(-1)
+    comp = engine.InverseFactorization(130, d, 3, torch.float64)
+    comp.run_loo(loss, kd, C, kd.n_hyp + 1, C[kd.n_hyp:], kd.n_hyp + 1, _dev(x), 0, _dev(y).reshape(1, -1), 0)
+    for u, v in zip(a, comp.loo_results()):
+        assert torch.equal(u, v)
+
+
+RAGGED = (97, 40, 130)
+
+
+def _ragged(sizes, fill, which=None):
+    """RaggedInverseFactorization of members ``which`` of RAGGED (all: None), X and y past each member's count filled
+    with ``fill``."""
+    tree, hyps, noises, d = PROGRAMS["ADD_SE_PER"]
+    kd = engine.kernel_descriptor(_kernel(tree, d), d)
+    idx = list(range(len(RAGGED))) if which is None else list(which)
+    n, B = max(sizes), len(sizes)
+    X, Y, H = np.full((B, n, d), fill), np.full((B, n), fill), np.zeros((B, nat.MAX_HYP))
+    for b, k in enumerate(idx):
+        x, y = _data("ADD_SE_PER", RAGGED[k])
+        X[b, :sizes[b]], Y[b, :sizes[b]], H[b, :kd.n_hyp] = x, y, hyps[k]
+    fac = engine.RaggedInverseFactorization(list(sizes), d, torch.float64)
+    fac.run_packed([kd] * B, _dev(H), _dev(np.array([noises[k] for k in idx])), _dev(X), _dev(Y), gradient=False)
+    return fac
+
+
+@pytest.mark.parametrize("loss", LOSSES)
+def test_ragged_members_equal_themselves_alone(loss):
+    """Members (97, 40, 130) from one set of launches: each against its reference, bit for bit what the member gives
+    when it is run alone, and not a bit different with X and y past each member's count filled with 1e6."""
+    res, facs = {}, {}
+    for fill in (0.0, 1e6):
+        fac = facs[fill] = _ragged(RAGGED, fill)
+        f, grads, mu, var = fac.loo(loss)
+        assert not fac.info.cpu().numpy().any()
+        res[fill] = (f.clone(), torch.stack(grads).clone(), mu.clone(), var.clone())
+    for u, v in zip(res[0.0], res[1e6]):
+        assert torch.equal(u, v)
+    f, g, mu, var = res[0.0]
+    for b, nb in enumerate(RAGGED):
+        f_ref, g_ref, mu_ref, var_ref = _reference("ADD_SE_PER", nb, loss, b)
+        ls.assert_value_close(float(f[b]), f_ref, "ragged member %d" % b)
+        ls.assert_grad_close(g[b].cpu().numpy(), g_ref, "ragged member %d" % b)
+        ls.assert_pred_close(mu[b, :nb].cpu().numpy(), mu_ref, "mu")
+        ls.assert_pred_close(var[b, :nb].cpu().numpy(), var_ref, "var")
+        assert not mu[b, nb:].any() and not var[b, nb:].any()          # zeros past the member's count
+        alone = _ragged([nb], 0.0, which=[b])
+        fa, ga, mua, vara = alone.loo(loss)
+        same_factor = torch.equal(alone.k_inv(0), facs[0.0].k_inv(b))
+        print("member %d alone: factorisation bitwise equal %s" % (b, same_factor))
+        assert torch.equal(fa[0], f[b]) and torch.equal(ga[0], g[b])
+        assert torch.equal(mua[0, :nb], mu[b, :nb]) and torch.equal(vara[0, :nb], var[b, :nb])
+
+
+@pytest.mark.parametrize("loss", LOSSES)
+def test_failed_member_is_inf_and_nan_and_leaves_the_others_alone(loss):
+    """Member 1 with a negative noise (K - I is indefinite): +inf and NaN for it; the others' bits are those of the
+    batch in which every member factors."""
+    good = _factor("ADD_SE_PER", 97)
+    fg, gg, mug, varg = [t.clone() for t in good.loo(loss)]
+    cands = _candidates("ADD_SE_PER")
+    cands[1, -1] = -1.0
+    bad = _factor("ADD_SE_PER", 97, cands)
+    f, g, mu, var = bad.loo(loss)
+    info = bad.info.cpu().numpy()
+    assert info[0] == 0 and info[1] != 0 and info[2] == 0
+    assert math.isinf(float(f[1])) and float(f[1]) > 0
+    assert bool(torch.isnan(g[1]).all()) and bool(torch.isnan(mu[1]).all()) and bool(torch.isnan(var[1]).all())
+    for b in (0, 2):
+        assert torch.equal(f[b], fg[b]) and torch.equal(g[b], gg[b])
+        assert torch.equal(mu[b], mug[b]) and torch.equal(var[b], varg[b])
+
+
+@pytest.mark.parametrize("loss,metric_type", [(ls.LPD, MetricType.LL), (ls.MSE, MetricType.MSE)])
+def test_metric_and_evaluator_give_the_engine_numbers(loss, metric_type):
+    name, n = "ADD_SE_PER", 97
+    tree, hyps, noises, d = PROGRAMS[name]
+    x, y = _data(name, n)
+    fac = _factor(name, n)
+    f, g, mu, var = [t.cpu().numpy().copy() for t in fac.loo(loss)]
+    kernel = _kernel(tree, d)
+    # the evaluator: candidate rows read in place, (f, g, info)
+    ev = sweep.native_batched_loo_value_and_gradient(kernel, _dev(x), _dev(y), loss)
+    assert ev.n_par == 4
+    C = _dev(_candidates(name))
+    for settle in (True, False):
+        fe, ge, info = ev(C, settle=settle)
+        assert not info.cpu().numpy().any()
+        assert np.array_equal(fe.cpu().numpy(), f) and np.array_equal(ge.cpu().numpy(), g)
+    with pytest.raises(ValueError, match="candidate rows must have 4 values"):
+        ev(C[:, :3].contiguous())
+    # the metric: one candidate at a time (a single evaluation may take the persistent factorisation: the bars, not bits)
+    di = DataInput(x, y.reshape(-1, 1), x, y.reshape(-1, 1))
+    di.set_mean_function(ZeroMeanFunction(d))
+    gpr = GaussianProcess(kernel, ZeroMeanFunction(d))
+    gpr.set_data_input(di)
+    metric = LeaveOneOut(di, gpr.covariance_matrix, mht.MatrixApproximations.NONE,
+                         mht.NumericalMatrixHandlingType.CHOLESKY_BASED, loss=metric_type)
+    hl, nz = hyp_list(hyps[0]), torch.tensor(noises[0], dtype=torch.float64)
+    f_ref, g_ref, mu_ref, var_ref = _reference(name, n, loss, 0)
+    v = metric.get_metric(hl, nz)
+    assert tuple(v.shape) == (1, 1)
+    ls.assert_value_close(float(v), f_ref, "metric")
+    assert abs(float(v) - f[0]) <= 1e-12 * abs(f[0])
+    v2, grads, gn = metric.get_metric_and_gradient(hl, nz)
+    assert [tuple(a.shape) for a in grads] == [tuple(h.shape) for h in hl]
+    gm = np.concatenate([a.cpu().numpy().reshape(-1) for a in grads] + [[float(gn)]])
+    ls.assert_grad_close(gm, g_ref, "metric")
+    assert abs(float(v2) - float(v)) <= 1e-12 * abs(float(v))
+    flat = metric.get_gradients(hl, nz).cpu().numpy()
+    assert flat.shape == g_ref[:-1].shape and np.max(np.abs(flat - g_ref[:-1])) <= ls.grad_bar(g_ref)
+    pm, pv = metric.get_predictions(hl, nz)
+    ls.assert_pred_close(pm.cpu().numpy(), mu_ref, "metric mu")
+    ls.assert_pred_close(pv.cpu().numpy(), var_ref, "metric var")
+
+
+def test_predictions_with_a_linear_mean_function():
+    """The targets are detrended with m(x) = 2.5 x, the LOO runs on the residual, and get_predictions adds m(x_i) back:
+    against the restatement on y - m(x), plus m(x)."""
+    name, n = "SE", 97
+    tree, hyps, noises, d = PROGRAMS[name]
+    x, y0 = _data(name, n)
+    slope = 2.5
+    y = y0 + slope * x[:, 0]
+    mean = LinearMeanFunction(1)
+    mean.set_last_hyper_parameter([torch.tensor([slope], dtype=torch.float64)])
+    di = DataInput(x, y.reshape(-1, 1), x, y.reshape(-1, 1))
+    di.set_mean_function(mean)
+    kernel = _kernel(tree, d)
+    gpr = GaussianProcess(kernel, mean)
+    gpr.set_data_input(di)
+    metric = LeaveOneOut(di, gpr.covariance_matrix, loss=MetricType.LL)
+    hl, nz = hyp_list(hyps[0]), torch.tensor(noises[0], dtype=torch.float64)
+    resid = y - slope * x[:, 0]
+    f_ref, _, mu_ref, var_ref = ls.loo_autodiff(tree, hyps[0], noises[0], x, resid, ls.LPD)
+    ls.assert_value_close(float(metric.get_metric(hl, nz)), f_ref, "detrended")
+    pm, pv = metric.get_predictions(hl, nz)
+    ls.assert_pred_close(pm.cpu().numpy(), mu_ref + slope * x[:, 0], "mu + mean")
+    ls.assert_pred_close(pv.cpu().numpy(), var_ref, "var")
+    assert float(np.max(np.abs(slope * x[:, 0]))) > 1.0      # (the mean that is added back is far above the bar)

@@ -566,7 +566,7 @@ static int assemble_impl(const gpk_kdesc* kd, const gpk_layout* lay, const doubl
   a.y_row = lay->y_row;
   a.p = lay->p;
   a.d = (int32_t)lay->d;
-  a.dp = (lay->d % 2 == 0) ? (int32_t)lay->d + 1 : (int32_t)lay->d;
+  a.dp = padded_dim(lay->d);
   a.plain = 0;
   a.eye = eye ? 1 : 0;
   a.ntile = lay->p / ATILE;
@@ -969,6 +969,83 @@ size_t gpk_grad_workspace_bytes(const gpk_kdesc* kd, const gpk_layout* lay) {
   return (size_t)lay->batch * (size_t)(nt * (nt + 1) / 2) * (size_t)(kd->n_hyp + 1) * sizeof(double);
 }
 
+// the tile pass's arguments over the points of a layout planned with m = n (part: [batch][tiles][n_hyp + 1]; n_dev:
+// ragged members' sizes or NULL); the caller adds what addresses the weights (W, ld, w_bs)
+static GradArgs grad_args(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_dev, int64_t hyp_stride,
+                          const double* X, int64_t x_bstride, const int64_t* n_dev, const int32_t* info_dev,
+                          double* part, double* grad_dev) {
+  GradArgs g;
+  memset(&g, 0, sizeof(g));
+  g.n = lay->n;
+  g.n_pad = lay->n_pad;
+  g.y_row = lay->y_row;
+  g.hyp = hyp_dev;
+  g.hyp_stride = hyp_stride;
+  g.X = X;
+  g.x_bs = x_bstride;
+  g.d = (int32_t)lay->d;
+  g.dp = padded_dim(lay->d);
+  g.ntile = (lay->n + ATILE - 1) / ATILE;
+  g.part = part;
+  g.grad = grad_dev;
+  g.info = info_dev;
+  g.nb = n_dev;
+  adjoint_masks(*kd, g.adj_mask);
+  return g;
+}
+
+// the -LML tile pass on a factored identity-augmented W (the entries check their arguments first)
+static int grad_pass(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_dev, int64_t hyp_stride,
+                     const double* X, int64_t x_bstride, const int64_t* n_dev, const void* W, const int32_t* info_dev,
+                     double* grad_dev, void* work, hipStream_t s) {
+  GradArgs g = grad_args(kd, lay, hyp_dev, hyp_stride, X, x_bstride, n_dev, info_dev, static_cast<double*>(work),
+                         grad_dev);
+  g.W = W;
+  g.ld = lay->ld;
+  g.w_bs = lay->w_batch_stride;
+  GPK_HIP(timed(6, 0.0, 0.0, s, [&] { return launch_grad(*kd, g, lay->dtype, lay->batch, s); }), "grad");
+  return 0;
+}
+
+// info cleared, K build with identity extra rows, factorisation: uniform, or ragged with the members' sizes n_dev
+static int factor_identity(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_dev, int64_t hyp_stride,
+                           const double* noise_dev, int64_t noise_stride, const double* X, int64_t x_bstride,
+                           const double* y, int64_t y_bstride, const int64_t* n_dev, void* W, void* Winv,
+                           int32_t* info_dev, void* stream) {
+  GPK_HIP(hipMemsetAsync(info_dev, 0, sizeof(int32_t) * lay->batch, reinterpret_cast<hipStream_t>(stream)),
+          "memset info");
+  if (n_dev) {
+    if (int e = gpk_assemble_inverse_ragged(kd, lay, hyp_dev, hyp_stride, noise_dev, noise_stride, X, x_bstride, y,
+                                            y_bstride, n_dev, W, stream))
+      return e;
+    return gpk_potrf_aug_ragged_ex(lay, W, Winv, info_dev, GPK_AUG_EXTRA_IDENTITY, n_dev, n_dev, stream);
+  }
+  if (int e = gpk_assemble_inverse(kd, lay, hyp_dev, hyp_stride, noise_dev, noise_stride, X, x_bstride, y, y_bstride,
+                                   W, stream))
+    return e;
+  return gpk_potrf_aug_ex(lay, W, Winv, info_dev, GPK_AUG_EXTRA_IDENTITY, stream);
+}
+
+// the same with test points as extra rows (uniform, or ragged with n_dev and m_dev)
+static int factor_test_rows(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_dev, int64_t hyp_stride,
+                            const double* noise_dev, int64_t noise_stride, const double* X, int64_t x_bstride,
+                            const double* Xs, int64_t xs_bstride, const double* y, int64_t y_bstride,
+                            const int64_t* n_dev, const int64_t* m_dev, void* W, void* Winv, int32_t* info_dev,
+                            void* stream) {
+  GPK_HIP(hipMemsetAsync(info_dev, 0, sizeof(int32_t) * lay->batch, reinterpret_cast<hipStream_t>(stream)),
+          "memset info");
+  if (n_dev) {
+    if (int e = gpk_assemble_ragged(kd, lay, hyp_dev, hyp_stride, noise_dev, noise_stride, X, x_bstride, Xs,
+                                    xs_bstride, y, y_bstride, n_dev, m_dev, W, stream))
+      return e;
+    return gpk_potrf_aug_ragged(lay, W, Winv, info_dev, n_dev, m_dev, stream);
+  }
+  if (int e = gpk_assemble(kd, lay, hyp_dev, hyp_stride, noise_dev, noise_stride, X, x_bstride, Xs, xs_bstride,
+                           nullptr, 0, y, y_bstride, W, stream))
+    return e;
+  return gpk_potrf_aug(lay, W, Winv, info_dev, stream);
+}
+
 int gpk_nlml_grad(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_dev, int64_t hyp_stride,
                   const double* noise_dev, int64_t noise_stride, const double* X, int64_t x_bstride,
                   const double* y, int64_t y_bstride, void* W, void* Winv, int32_t* info_dev,
@@ -980,37 +1057,13 @@ int gpk_nlml_grad(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_
   if (!out_dev) return fail_arg(14, "out_dev");
   if (grad_dev && (!work || work_bytes < gpk_grad_workspace_bytes(kd, lay)))
     return fail_arg(16, "work (see gpk_grad_workspace_bytes)");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  GPK_HIP(hipMemsetAsync(info_dev, 0, sizeof(int32_t) * lay->batch, s), "memset info");
-  int e = gpk_assemble_inverse(kd, lay, hyp_dev, hyp_stride, noise_dev, noise_stride, X, x_bstride, y,
-                               y_bstride, W, stream);
-  if (e) return e;
-  e = gpk_potrf_aug_ex(lay, W, Winv, info_dev, GPK_AUG_EXTRA_IDENTITY, stream);
-  if (e) return e;
-  e = gpk_finalize(lay, W, info_dev, out_dev, nullptr, nullptr, stream);
-  if (e) return e;
+  if (int e = factor_identity(kd, lay, hyp_dev, hyp_stride, noise_dev, noise_stride, X, x_bstride, y, y_bstride,
+                              nullptr, W, Winv, info_dev, stream))
+    return e;
+  if (int e = gpk_finalize(lay, W, info_dev, out_dev, nullptr, nullptr, stream)) return e;
   if (!grad_dev) return 0;
-  GradArgs g;
-  memset(&g, 0, sizeof(g));
-  g.W = W;
-  g.ld = lay->ld;
-  g.w_bs = lay->w_batch_stride;
-  g.n = lay->n;
-  g.n_pad = lay->n_pad;
-  g.y_row = lay->y_row;
-  g.hyp = hyp_dev;
-  g.hyp_stride = hyp_stride;
-  g.X = X;
-  g.x_bs = x_bstride;
-  g.d = (int32_t)lay->d;
-  g.dp = (lay->d % 2 == 0) ? (int32_t)lay->d + 1 : (int32_t)lay->d;
-  g.ntile = (lay->n + ATILE - 1) / ATILE;
-  g.part = static_cast<double*>(work);
-  g.grad = grad_dev;
-  g.info = info_dev;
-  adjoint_masks(*kd, g.adj_mask);
-  GPK_HIP(timed(6, 0.0, 0.0, s, [&] { return launch_grad(*kd, g, lay->dtype, lay->batch, s); }), "grad");
-  return 0;
+  return grad_pass(kd, lay, hyp_dev, hyp_stride, X, x_bstride, nullptr, W, info_dev, grad_dev, work,
+                   reinterpret_cast<hipStream_t>(stream));
 }
 
 // ---------------------------------------------------------------- ragged identity-augmented batches
@@ -1047,29 +1100,8 @@ int gpk_grad_ragged(const gpk_kdesc* kd, const gpk_layout* lay, const double* hy
   if (!grad_dev) return fail_arg(10, "grad_dev");
   if (!work || work_bytes < gpk_grad_workspace_bytes(kd, lay))
     return fail_arg(11, "work (see gpk_grad_workspace_bytes)");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  GradArgs g;
-  memset(&g, 0, sizeof(g));
-  g.W = W;
-  g.ld = lay->ld;
-  g.w_bs = lay->w_batch_stride;
-  g.n = lay->n;
-  g.n_pad = lay->n_pad;
-  g.y_row = lay->y_row;
-  g.hyp = hyp_dev;
-  g.hyp_stride = hyp_stride;
-  g.X = X;
-  g.x_bs = x_bstride;
-  g.d = (int32_t)lay->d;
-  g.dp = (lay->d % 2 == 0) ? (int32_t)lay->d + 1 : (int32_t)lay->d;
-  g.ntile = (lay->n + ATILE - 1) / ATILE;
-  g.part = static_cast<double*>(work);
-  g.grad = grad_dev;
-  g.info = info_dev;
-  g.nb = n_dev;
-  adjoint_masks(*kd, g.adj_mask);
-  GPK_HIP(timed(6, 0.0, 0.0, s, [&] { return launch_grad(*kd, g, lay->dtype, lay->batch, s); }), "grad");
-  return 0;
+  return grad_pass(kd, lay, hyp_dev, hyp_stride, X, x_bstride, n_dev, W, info_dev, grad_dev, work,
+                   reinterpret_cast<hipStream_t>(stream));
 }
 
 int gpk_nlml_grad_ragged(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_dev, int64_t hyp_stride,
@@ -1085,15 +1117,10 @@ int gpk_nlml_grad_ragged(const gpk_kdesc* kd, const gpk_layout* lay, const doubl
   if (!out_dev) return fail_arg(15, "out_dev");
   if (grad_dev && (!work || work_bytes < gpk_grad_workspace_bytes(kd, lay)))
     return fail_arg(17, "work (see gpk_grad_workspace_bytes)");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  GPK_HIP(hipMemsetAsync(info_dev, 0, sizeof(int32_t) * lay->batch, s), "memset info");
-  int e = gpk_assemble_inverse_ragged(kd, lay, hyp_dev, hyp_stride, noise_dev, noise_stride, X, x_bstride, y,
-                                      y_bstride, n_dev, W, stream);
-  if (e) return e;
-  e = gpk_potrf_aug_ragged_ex(lay, W, Winv, info_dev, GPK_AUG_EXTRA_IDENTITY, n_dev, n_dev, stream);
-  if (e) return e;
-  e = gpk_finalize_ragged(lay, W, info_dev, n_dev, out_dev, nullptr, nullptr, stream);
-  if (e) return e;
+  if (int e = factor_identity(kd, lay, hyp_dev, hyp_stride, noise_dev, noise_stride, X, x_bstride, y, y_bstride,
+                              n_dev, W, Winv, info_dev, stream))
+    return e;
+  if (int e = gpk_finalize_ragged(lay, W, info_dev, n_dev, out_dev, nullptr, nullptr, stream)) return e;
   if (!grad_dev) return 0;
   return gpk_grad_ragged(kd, lay, hyp_dev, hyp_stride, X, x_bstride, n_dev, W, info_dev, grad_dev, work, work_bytes,
                          stream);
@@ -1151,7 +1178,7 @@ int gpk_mse_backward(const gpk_kdesc* kd, const gpk_layout* lay, const double* h
   g.ys = ys;
   g.ys_bs = ys_bstride;
   g.d = (int32_t)lay->d;
-  g.dp = (lay->d % 2 == 0) ? (int32_t)lay->d + 1 : (int32_t)lay->d;
+  g.dp = padded_dim(lay->d);
   g.ntr = (lay->n + ATILE - 1) / ATILE;
   g.nte = (lay->m + ATILE - 1) / ATILE;
   g.rhs = static_cast<double*>(work);
@@ -1213,21 +1240,9 @@ int gpk_mse_grad(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_d
   if (!grad_dev) return fail_arg(21, "grad_dev");
   if (!work || work_bytes < gpk_mse_grad_workspace_bytes(kd, lay))
     return fail_arg(22, "work (see gpk_mse_grad_workspace_bytes)");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  GPK_HIP(hipMemsetAsync(info_dev, 0, sizeof(int32_t) * lay->batch, s), "memset info");
-  int e;
-  if (n_dev) {
-    e = gpk_assemble_ragged(kd, lay, hyp_dev, hyp_stride, noise_dev, noise_stride, X, x_bstride, Xs, xs_bstride, y,
-                            y_bstride, n_dev, m_dev, W, stream);
-    if (e) return e;
-    e = gpk_potrf_aug_ragged(lay, W, Winv, info_dev, n_dev, m_dev, stream);
-  } else {
-    e = gpk_assemble(kd, lay, hyp_dev, hyp_stride, noise_dev, noise_stride, X, x_bstride, Xs, xs_bstride, nullptr, 0,
-                     y, y_bstride, W, stream);
-    if (e) return e;
-    e = gpk_potrf_aug(lay, W, Winv, info_dev, stream);
-  }
-  if (e) return e;
+  if (int e = factor_test_rows(kd, lay, hyp_dev, hyp_stride, noise_dev, noise_stride, X, x_bstride, Xs, xs_bstride, y,
+                               y_bstride, n_dev, m_dev, W, Winv, info_dev, stream))
+    return e;
   // (the read-out: gpk_mse_backward's first kernel reads -mu from the corner's y row, where gpk_finalize reads it;
   // every argument it checks was checked above)
   return gpk_mse_backward(kd, lay, hyp_dev, hyp_stride, X, x_bstride, Xs, xs_bstride, ys, ys_bstride, n_dev, m_dev, W,
@@ -1302,23 +1317,8 @@ int gpk_loo_backward(int32_t loss, const gpk_kdesc* kd, const gpk_layout* lay, c
                 [&] { return launch_loo_symv(g, lay->batch, s); }),
           "loo symv");
   GPK_HIP(timed(3, nn * nn * nn * lay->batch, 0.0, s, [&] { return launch_loo_cot(g, lay->batch, s); }), "loo cot");
-  GradArgs gg;
-  memset(&gg, 0, sizeof(gg));
-  gg.n = lay->n;
-  gg.n_pad = lay->n_pad;
-  gg.y_row = lay->y_row;
-  gg.hyp = hyp_dev;
-  gg.hyp_stride = hyp_stride;
-  gg.X = X;
-  gg.x_bs = x_bstride;
-  gg.d = (int32_t)lay->d;
-  gg.dp = (lay->d % 2 == 0) ? (int32_t)lay->d + 1 : (int32_t)lay->d;
-  gg.ntile = (lay->n + ATILE - 1) / ATILE;
-  gg.part = g.slab + loo_slab_elems(lay) + loo_cot_elems(lay);
-  gg.grad = grad_dev;
-  gg.info = info_dev;
-  gg.nb = n_dev;
-  adjoint_masks(*kd, gg.adj_mask);
+  const GradArgs gg = grad_args(kd, lay, hyp_dev, hyp_stride, X, x_bstride, n_dev, info_dev,
+                                g.slab + loo_slab_elems(lay) + loo_cot_elems(lay), grad_dev);
   GPK_HIP(timed(6, 0.0, 0.0, s,
                 [&] {
                   return launch_grad_cot(*kd, gg, g.cot, lay->n_pad, (lay->n_pad + 1) * lay->n_pad, lay->n_pad,
@@ -1343,21 +1343,9 @@ int gpk_loo_grad(int32_t loss, const gpk_kdesc* kd, const gpk_layout* lay, const
   if (!out_dev) return fail_arg(16, "out_dev");
   if (!work || work_bytes < gpk_loo_workspace_bytes(kd, lay))
     return fail_arg(20, "work (see gpk_loo_workspace_bytes)");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  GPK_HIP(hipMemsetAsync(info_dev, 0, sizeof(int32_t) * lay->batch, s), "memset info");
-  int e;
-  if (n_dev) {
-    e = gpk_assemble_inverse_ragged(kd, lay, hyp_dev, hyp_stride, noise_dev, noise_stride, X, x_bstride, y, y_bstride,
-                                    n_dev, W, stream);
-    if (e) return e;
-    e = gpk_potrf_aug_ragged_ex(lay, W, Winv, info_dev, GPK_AUG_EXTRA_IDENTITY, n_dev, n_dev, stream);
-  } else {
-    e = gpk_assemble_inverse(kd, lay, hyp_dev, hyp_stride, noise_dev, noise_stride, X, x_bstride, y, y_bstride, W,
-                             stream);
-    if (e) return e;
-    e = gpk_potrf_aug_ex(lay, W, Winv, info_dev, GPK_AUG_EXTRA_IDENTITY, stream);
-  }
-  if (e) return e;
+  if (int e = factor_identity(kd, lay, hyp_dev, hyp_stride, noise_dev, noise_stride, X, x_bstride, y, y_bstride, n_dev,
+                              W, Winv, info_dev, stream))
+    return e;
   return gpk_loo_backward(loss, kd, lay, hyp_dev, hyp_stride, X, x_bstride, y, y_bstride, n_dev, W, info_dev, out_dev,
                           mu_dev, var_dev, grad_dev, work, work_bytes, stream);
 }
@@ -1387,7 +1375,7 @@ int gpk_kernel_matrix(const gpk_kdesc* kd, const double* hyp_dev, int dtype, int
   a.n = n;
   a.m = m;
   a.d = d;
-  a.dp = (d % 2 == 0) ? d + 1 : d;
+  a.dp = padded_dim(d);
   a.plain = 1;
   a.uplo = uplo;
   a.diag_add = diag_add;

@@ -2,7 +2,9 @@
 // kernel matrix (gpk_kernel_vjp: vjp_kernel) and the gradient of the held-out mean squared error (gpk_mse_backward:
 // mse_tile_kernel).  All walk 64 x 64 tiles staged as the K build stages them (gpk_stage.h) and re-evaluate the
 // program per element with the reference's literal formulas (base_values, gpk_kernels.h).  launch_grad_cot runs
-// grad_kernel over a cotangent buffer instead of W's corner (the leave-one-out gradient, gpk_loo.hip): a host launcher.
+// grad_kernel over a cotangent buffer instead of W's corner (the leave-one-out gradient, gpk_loo.hip): a host launcher,
+// launch_grad_tiles with five fields swapped.  The host side of the tile passes is said once (stage_args,
+// tile_lds_bytes, launch_tiles_then_reduce, at the end of this file).
 // Two things are written more than once here on purpose, in the same words, and a change to one belongs in the others
 // (profiles/grad_split_codegen.txt, profiles/grad_split_ab.txt):
 // - the three kernels' loops over the program's leaves (adjoint product over adj_mask, base_partials, the leaf's
@@ -831,45 +833,62 @@ hipError_t launch_mse_residual(const MseArgs& g, int32_t batch, hipStream_t s) {
   return hipGetLastError();
 }
 
-hipError_t launch_mse_tiles(const gpk_kdesc& kd, const MseArgs& g, int32_t batch, hipStream_t s) {
-  // the staging helpers read the points through an augmented-layout AsmArgs (test rows from Xs)
+// ---- host side of the two tile passes (grad_kernel, mse_tile_kernel): one statement of what they share
+// the AsmArgs the staging helpers (stage_points) read the points through, an augmented layout: the fields GradArgs and
+// MseArgs both carry, m extra rows, and -- ragged (nb / mb NULL: uniform) -- the members' own counts, which bound
+// the points stage_points reads (member_n / member_m)
+template <class G>
+static AsmArgs stage_args(const G& g, int64_t m, const int64_t* mb) {
   AsmArgs a;
   memset(&a, 0, sizeof(a));
   a.hyp = g.hyp;
   a.hyp_stride = g.hyp_stride;
   a.X = g.X;
   a.x_bs = g.x_bs;
-  a.Xs = g.Xs;
-  a.xs_bs = g.xs_bs;
   a.n = g.n;
-  a.m = g.m;
+  a.m = m;
   a.n_pad = g.n_pad;
   a.y_row = g.y_row;
   a.d = g.d;
   a.dp = g.dp;
-  a.nb = g.nb;  // ragged (NULL: uniform): member_n / member_m bound the points stage_points reads
-  a.mb = g.mb;
-  const int64_t ntile = g.ntr * (g.ntr + 1) / 2 + g.nte * g.ntr;
+  a.nb = g.nb;
+  a.mb = mb;
+  return a;
+}
+
+// dynamic LDS of a tile pass: the hyperparameters, row_vectors 64-vectors of weights (grad_kernel 2, mse_tile_kernel
+// 4), the reduction scratch, the two edges' staged points and -- programs with products -- every node's values
+static size_t tile_lds_bytes(const gpk_kdesc& kd, const uint32_t* adj_mask, int32_t dp, int row_vectors) {
   bool has_mul = false;
-  for (int q = 0; q < kd.n_nodes; ++q) has_mul |= g.adj_mask[q] != 0u;
-  const size_t lds = sizeof(double) * (GPK_MAX_HYP + 4 * ATILE + 4 * (GNP + 1) +
-                                       2 * (size_t)(1 + kd.n_ard) * ATILE * a.dp +
-                                       (has_mul ? (size_t)kd.n_nodes * 256 : 0));
-  dim3 grid((unsigned)ntile, (unsigned)batch, 1);
+  for (int q = 0; q < kd.n_nodes; ++q) has_mul |= adj_mask[q] != 0u;
+  return sizeof(double) * (GPK_MAX_HYP + (size_t)row_vectors * ATILE + 4 * (GNP + 1) +
+                           2 * (size_t)(1 + kd.n_ard) * ATILE * dp + (has_mul ? (size_t)kd.n_nodes * 256 : 0));
+}
+
+// the tile kernel over ntile x batch workgroups, then its reduction of the per-tile partial sums (fixed order)
+template <class Tile, class Reduce, class G>
+static hipError_t launch_tiles_then_reduce(Tile tile, Reduce reduce, const gpk_kdesc& kd, const AsmArgs& a, const G& g,
+                                           int64_t ntile, size_t lds, int32_t batch, hipStream_t s) {
+  hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(tile), lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(tile, dim3((unsigned)ntile, (unsigned)batch, 1), dim3(256), lds, s, kd, a, g);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(reduce, dim3((unsigned)(kd.n_hyp + 1), (unsigned)batch), dim3(256), 0, s, g, ntile,
+                     kd.n_hyp + 1);
+  return hipGetLastError();
+}
+
+hipError_t launch_mse_tiles(const gpk_kdesc& kd, const MseArgs& g, int32_t batch, hipStream_t s) {
+  AsmArgs a = stage_args(g, g.m, g.mb);  // (test rows from Xs)
+  a.Xs = g.Xs;
+  a.xs_bs = g.xs_bs;
   // (a program with a rational quadratic leaf: the instantiation that carries the leaf's code, rq_leaves)
   const bool rq = rq_leaves(kd) > 0;
   const auto tile = g.nb != nullptr ? (rq ? mse_tile_kernel<true, true> : mse_tile_kernel<false, true>)
                                     : (rq ? mse_tile_kernel<true, false> : mse_tile_kernel<false, false>);
-  {
-    hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(tile), lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(tile, grid, dim3(256), lds, s, kd, a, g);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(mse_reduce_kernel, dim3((unsigned)(kd.n_hyp + 1), (unsigned)batch), dim3(256), 0, s, g, ntile,
-                     kd.n_hyp + 1);
-  return hipGetLastError();
+  return launch_tiles_then_reduce(tile, mse_reduce_kernel, kd, a, g, g.ntr * (g.ntr + 1) / 2 + g.nte * g.ntr,
+                                  tile_lds_bytes(kd, g.adj_mask, g.dp, 4), batch, s);
 }
 
 size_t vjp_workspace_elems(const gpk_kdesc& kd, int64_t n, int64_t m, int32_t d, bool want_z) {
@@ -887,7 +906,7 @@ hipError_t launch_vjp(const gpk_kdesc& kd, const VjpArgs& g0, const double* X, i
   a.n = n;
   a.m = m;
   a.d = d;
-  a.dp = (d % 2 == 0) ? d + 1 : d;
+  a.dp = padded_dim(d);
   a.plain = 1;
   VjpArgs g = g0;
   g.want_z = grad_z != nullptr ? 1 : 0;
@@ -925,30 +944,11 @@ hipError_t launch_vjp(const gpk_kdesc& kd, const VjpArgs& g0, const double* X, i
   return hipSuccess;
 }
 
-hipError_t launch_grad(const gpk_kdesc& kd, const GradArgs& g, int dtype, int32_t batch, hipStream_t s) {
-  // the staging helpers read the points through an augmented-layout AsmArgs
-  AsmArgs a;
-  memset(&a, 0, sizeof(a));
-  a.hyp = g.hyp;
-  a.hyp_stride = g.hyp_stride;
-  a.X = g.X;
-  a.x_bs = g.x_bs;
-  a.n = g.n;
-  a.m = g.n;
-  a.n_pad = g.n_pad;
-  a.y_row = g.y_row;
-  a.d = g.d;
-  a.dp = g.dp;
+// grad_kernel over the points of ``pts`` (its n, n_pad, y_row: the real layout; m_b = n_b) with the weights g addresses
+static hipError_t launch_grad_tiles(const gpk_kdesc& kd, const GradArgs& pts, const GradArgs& g, int dtype,
+                                    int32_t batch, hipStream_t s) {
+  AsmArgs a = stage_args(pts, pts.n, pts.nb);
   a.eye = 1;
-  a.nb = g.nb;  // ragged (NULL: uniform): member_n / member_m bound the points stage_points reads (m_b = n_b)
-  a.mb = g.nb;
-  const int64_t ntri = g.ntile * (g.ntile + 1) / 2;
-  bool has_mul = false;
-  for (int q = 0; q < kd.n_nodes; ++q) has_mul |= g.adj_mask[q] != 0u;
-  const size_t lds = sizeof(double) * (GPK_MAX_HYP + 2 * ATILE + 4 * (GNP + 1) +
-                                       2 * (size_t)(1 + kd.n_ard) * ATILE * a.dp +
-                                       (has_mul ? (size_t)kd.n_nodes * 256 : 0));
-  dim3 grid((unsigned)ntri, (unsigned)batch, 1);
   // (a program with a rational quadratic leaf: the instantiation that carries the leaf's code, rq_leaves)
   const bool rq = rq_leaves(kd) > 0;
   const auto grad =
@@ -957,16 +957,12 @@ hipError_t launch_grad(const gpk_kdesc& kd, const GradArgs& g, int dtype, int32_
                               : (rq ? grad_kernel<float, true, true> : grad_kernel<float, false, true>))
           : (dtype == GPK_F64 ? (rq ? grad_kernel<double, true> : grad_kernel<double, false>)
                               : (rq ? grad_kernel<float, true> : grad_kernel<float, false>));
-  {
-    hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(grad), lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(grad, grid, dim3(256), lds, s, kd, a, g);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)(kd.n_hyp + 1), (unsigned)batch), dim3(256), 0, s,
-                     g, ntri, kd.n_hyp + 1);
-  return hipGetLastError();
+  return launch_tiles_then_reduce(grad, grad_reduce_kernel, kd, a, g, g.ntile * (g.ntile + 1) / 2,
+                                  tile_lds_bytes(kd, g.adj_mask, g.dp, 2), batch, s);
+}
+
+hipError_t launch_grad(const gpk_kdesc& kd, const GradArgs& g, int dtype, int32_t batch, hipStream_t s) {
+  return launch_grad_tiles(kd, g, g, dtype, batch, s);
 }
 
 // launch_grad with the weights read from a cotangent buffer (gpk_loo_backward): the AsmArgs that stage_points reads
@@ -974,46 +970,13 @@ hipError_t launch_grad(const gpk_kdesc& kd, const GradArgs& g, int dtype, int32_
 // g.y_row: grad_kernel uses them for nothing else) carry the buffer's.  The kernels are launch_grad's f64 ones.
 hipError_t launch_grad_cot(const gpk_kdesc& kd, const GradArgs& g0, const double* C, int64_t c_ld, int64_t c_bs,
                            int64_t c_yrow, int32_t batch, hipStream_t s) {
-  AsmArgs a;
-  memset(&a, 0, sizeof(a));
-  a.hyp = g0.hyp;
-  a.hyp_stride = g0.hyp_stride;
-  a.X = g0.X;
-  a.x_bs = g0.x_bs;
-  a.n = g0.n;
-  a.m = g0.n;
-  a.n_pad = g0.n_pad;
-  a.y_row = g0.y_row;
-  a.d = g0.d;
-  a.dp = g0.dp;
-  a.eye = 1;
-  a.nb = g0.nb;
-  a.mb = g0.nb;
   GradArgs g = g0;
   g.W = C;
   g.ld = c_ld;
   g.w_bs = c_bs;
   g.n_pad = 0;
   g.y_row = c_yrow;
-  const int64_t ntri = g.ntile * (g.ntile + 1) / 2;
-  bool has_mul = false;
-  for (int q = 0; q < kd.n_nodes; ++q) has_mul |= g.adj_mask[q] != 0u;
-  const size_t lds = sizeof(double) * (GPK_MAX_HYP + 2 * ATILE + 4 * (GNP + 1) +
-                                       2 * (size_t)(1 + kd.n_ard) * ATILE * a.dp +
-                                       (has_mul ? (size_t)kd.n_nodes * 256 : 0));
-  const bool rq = rq_leaves(kd) > 0;
-  const auto grad = g.nb != nullptr ? (rq ? grad_kernel<double, true, true> : grad_kernel<double, false, true>)
-                                    : (rq ? grad_kernel<double, true> : grad_kernel<double, false>);
-  {
-    hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(grad), lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(grad, dim3((unsigned)ntri, (unsigned)batch, 1), dim3(256), lds, s, kd, a, g);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)(kd.n_hyp + 1), (unsigned)batch), dim3(256), 0, s,
-                     g, ntri, kd.n_hyp + 1);
-  return hipGetLastError();
+  return launch_grad_tiles(kd, g0, g, GPK_F64, batch, s);
 }
 
 }  // namespace gpk

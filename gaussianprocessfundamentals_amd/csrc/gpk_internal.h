@@ -35,6 +35,9 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 typedef float f4 __attribute__((ext_vector_type(4)));
 
 // ----------------------------------------------------------------------------------- launch args
+// LDS row stride of a staged point (AsmArgs::dp and its kin): odd when d is even, so that rows do not share a bank
+inline int32_t padded_dim(int64_t d) { return (int32_t)((d % 2 == 0) ? d + 1 : d); }
+
 struct AsmArgs {
   const double* hyp;
   int64_t hyp_stride;

@@ -12,6 +12,7 @@ All arithmetic runs in libgpk on the GPU; torch only allocates and views device 
 from __future__ import annotations
 
 import ctypes
+import functools
 import logging
 import os
 from typing import List, Optional, Sequence
@@ -356,6 +357,10 @@ class AugmentedFactorization:
         es = 8 if self.code == nat.GPK_F64 else 4
         self._pending = None   # (rerun, stream) of a persistent run not yet verified (see CHAIN_VERIFY)
         self._W = torch.empty(lay.w_bytes // es, dtype=self.dtype, device=dev)
+        self._dev = self._W.device   # (cached: every launch and result buffer asks for it)
+        # _new(*shape): a new fp64 result buffer per evaluation (the caching allocator's, no device work), so views of an
+        # earlier evaluation's results stay valid without a copy (LogLikelihood.get_metric returns one)
+        self._new = functools.partial(torch.empty, dtype=torch.float64, device=self._dev)
         self._Winv = torch.empty(max(1, lay.inv_bytes // es), dtype=self.dtype, device=dev)
         self._info = torch.zeros(self.batch, dtype=torch.int32, device=dev)
         self._out = torch.empty(self.batch * 4, dtype=torch.float64, device=dev)
@@ -364,7 +369,13 @@ class AugmentedFactorization:
         self.kd = None
         self.done = False
         self.shape_key = None
-        self._mse_work = self._mse_out = self._mse_grad = self._mse_operands = None
+        self.work = None            # the passes' workspace: grow-only, kept between calls (_workspace)
+        self._keep = (None, None)   # operand lifetimes: (the last run's, a later pass's) until the stream is past them
+        self._alphas = None
+        self._mse_operands = self._loo_operands = None
+        self._loo_out = None
+        self._results = {}          # run kind -> (read-out buffer, gradient or None, extras ...), see _record
+        self._record("nlml", self._out)
 
     # -- result buffers: every read settles a pending persistent run first ---------------------
     @property
@@ -403,7 +414,7 @@ class AugmentedFactorization:
         of a result verifies it (:meth:`_settle`).  No synchronisation here."""
         self._pending = None
         if CHAIN_VERIFY and nat.last_factorisation_was_chain():
-            self._pending = (rerun, torch.cuda.current_stream(self._W.device))
+            self._pending = (rerun, torch.cuda.current_stream(self._dev))
 
     def _settle(self) -> None:
         """Verify a pending persistent run: if a wait timed out (info = -1), run it again on the launch path on
@@ -423,65 +434,108 @@ class AugmentedFactorization:
             with nat.thread_tune(chain=0):
                 rerun()
 
+    def _enqueue(self, once, *args):
+        """Every run kind's launch: ``once(*args)`` now, and again from :meth:`_settle` should the persistent launch
+        it took time out.  Invariant: a ``once`` body reads the raw buffers ``_W`` / ``_Winv`` / ``_info`` (and
+        ``_out``, ``_mu``, ``_var``), never the settling properties -- a re-run must not settle itself."""
+        self._pending = None   # (the previous run's results are overwritten unread)
+        once(*args)
+        self._defer_verify(lambda: once(*args))
+        return self
+
+    def _check_operands(self, n_hyp, hyp, hyp_stride, noise, noise_stride, X, x_bstride, y, y_bstride,
+                        X_test=None, y_test=None) -> None:
+        """The device reads these extents blindly: check them here (an undersized operand would be read out of
+        bounds, not reported).  ``X_test`` / ``y_test``: (tensor, batch stride) where the run reads them."""
+        B, dev = self.batch, self._dev
+        _check_operand("hyper_parameter", hyp, hyp_stride, n_hyp, B, dev)
+        _check_operand("noise", noise, noise_stride, 1, B, dev)
+        _check_operand("X", X, x_bstride, self.n * self.d, B, dev)
+        _check_operand("y", y, y_bstride, self.n, B, dev)
+        if X_test is not None:
+            _check_operand("X_test", X_test[0], X_test[1], self.m * self.d, B, dev)
+        if y_test is not None:
+            _check_operand("y_test", y_test[0], y_test[1], self.m, B, dev)
+
+    def _workspace(self, need: int) -> torch.Tensor:
+        """At least ``need`` bytes of fp64 device workspace, kept between calls (it only grows).  One buffer serves
+        every pass of this factorisation: they follow each other on the stream."""
+        if self.work is None or self.work.numel() * 8 < need:
+            self.work = torch.empty(max(1, need // 8), dtype=torch.float64, device=self._dev)
+        return self.work
+
+    def _record(self, kind: str, out: torch.Tensor, grad=None, *extras) -> None:
+        """The one place a run kind ("nlml", "mse", "loo") keeps its results: the [B * 4] read-out buffer (column 0:
+        the value), the gradient [B, n_hyp + 1] or None, then extras (the LOO mu / var)."""
+        self._results[kind] = (out, grad) + extras
+
+    def _views(self, kind: str):
+        """(value [B], gradient or None, extras ...) of the last run of ``kind``, as recorded."""
+        r = self._results[kind]
+        return (r[0].view(self.batch, 4)[:, 0],) + r[1:]
+
+    def results(self, kind: str = "nlml", settle: bool = True):
+        """(f [B], g [B, n_hyp + 1] or None, info [B] int32) device views of the last run of ``kind``.  Settled: a
+        pending persistent run is verified first (:meth:`_settle`).  Unsettled: no host synchronisation, for callers
+        that pipeline runs and only forward the values on the device -- a wait that timed out shows as info = -1
+        there, and the run is not re-done."""
+        if settle:
+            self._settle()
+        r = self._results.get(kind)
+        if r is None:
+            raise RuntimeError({"mse": "run_mse(...) or mse_gradient(...) first",
+                                "loo": "run_loo(...) or loo(...) first"}[kind])
+        return r[0].view(self.batch, 4)[:, 0], r[1], self._info
+
     def run(self, kd: nat.GpkKdesc, hyp: torch.Tensor, hyp_stride: int, noise: torch.Tensor,
             noise_stride: int, X: torch.Tensor, x_bstride: int, y: torch.Tensor, y_bstride: int,
             Xs: Optional[torch.Tensor] = None, xs_bstride: int = 0,
             E: Optional[torch.Tensor] = None, e_bstride: int = 0):
         """Enqueue the factorisation (asynchronous: a persistent run is verified at the first read, see
         CHAIN_VERIFY)."""
-        args = (kd, hyp, hyp_stride, noise, noise_stride, X, x_bstride, y, y_bstride, Xs, xs_bstride, E, e_bstride)
-        self._pending = None   # (the previous run's results are overwritten unread)
-        self._run_once(*args)
-        self._defer_verify(lambda: self._run_once(*args))
-        return self
+        return self._enqueue(self._run_once, kd, hyp, hyp_stride, noise, noise_stride, X, x_bstride, y, y_bstride,
+                             Xs, xs_bstride, E, e_bstride)
 
     def _fresh_out(self) -> None:
-        """A new read-out buffer per evaluation (the caching allocator's, no device work): views of an earlier
-        evaluation's -LML stay valid without a copy (LogLikelihood.get_metric returns one)."""
-        self._out = torch.empty(self.batch * 4, dtype=torch.float64, device=self._W.device)
+        """A new -LML read-out buffer for this evaluation (see ``_new``), no gradient recorded yet."""
+        self._out = self._new(self.batch * 4)
+        self._record("nlml", self._out)
 
     def _run_once(self, kd, hyp, hyp_stride, noise, noise_stride, X, x_bstride, y, y_bstride, Xs, xs_bstride,
                   E, e_bstride):
         lay = self.layout
-        B, n, m, d = self.batch, self.n, self.m, self.d
+        B, n, m = self.batch, self.n, self.m
         self._alphas = None
         self._fresh_out()
-        # the device reads these extents blindly: check them here (an undersized operand would
-        # be read out of bounds, not reported)
-        _check_operand("hyper_parameter", hyp, hyp_stride, kd.n_hyp, B, self.W.device)
-        _check_operand("noise", noise, noise_stride, 1, B, self.W.device)
-        _check_operand("X", X, x_bstride, n * d, B, self.W.device)
-        _check_operand("y", y, y_bstride, n, B, self.W.device)
+        self._check_operands(kd.n_hyp, hyp, hyp_stride, noise, noise_stride, X, x_bstride, y, y_bstride,
+                             X_test=(Xs, xs_bstride) if m and E is None and Xs is not None else None)
         if m:
             if E is not None:
-                _check_operand("E", E, e_bstride, m * n, B, self.W.device)
-            elif Xs is not None:
-                _check_operand("X_test", Xs, xs_bstride, m * d, B, self.W.device)
-            else:
+                _check_operand("E", E, e_bstride, m * n, B, self._dev)
+            elif Xs is None:
                 raise ValueError("m = %d extra rows need X_test or E" % m)
-        s = nat.stream_handle(self.W.device)
+        s = nat.stream_handle(self._dev)
         L = self.L
         if m == 0:
             # gpk_nlml: K build (fused into the first trailing update for single-node kernels) +
             # factorisation + read-out; zeroes info itself
             nat.check(L.gpk_nlml(ctypes.byref(kd), ctypes.byref(lay), nat.ptr(hyp), hyp_stride, nat.ptr(noise),
-                                 noise_stride, nat.ptr(X), x_bstride, nat.ptr(y), y_bstride, nat.ptr(self.W),
-                                 nat.ptr(self.Winv), nat.ptr(self.info), nat.ptr(self.out), s), "gpk_nlml")
+                                 noise_stride, nat.ptr(X), x_bstride, nat.ptr(y), y_bstride, nat.ptr(self._W),
+                                 nat.ptr(self._Winv), nat.ptr(self._info), nat.ptr(self._out), s), "gpk_nlml")
             self.kd = kd
             self.done = True
             return self
-        self.info.zero_()
+        self._info.zero_()
         # (what mse_gradient needs of this run: kernel rows only -- explicit extra rows have no test points)
         self._mse_operands = (kd, hyp, hyp_stride, X, x_bstride, Xs, xs_bstride) if E is None else None
         nat.check(L.gpk_assemble(ctypes.byref(kd), ctypes.byref(lay), nat.ptr(hyp), hyp_stride,
                                  nat.ptr(noise), noise_stride, nat.ptr(X), x_bstride,
                                  nat.ptr(Xs), xs_bstride, nat.ptr(E), e_bstride,
-                                 nat.ptr(y), y_bstride, nat.ptr(self.W), s), "gpk_assemble")
-        nat.check(L.gpk_potrf_aug(ctypes.byref(lay), nat.ptr(self.W), nat.ptr(self.Winv),
-                                  nat.ptr(self.info), s), "gpk_potrf_aug")
-        nat.check(L.gpk_finalize(ctypes.byref(lay), nat.ptr(self.W), nat.ptr(self.info),
-                                 nat.ptr(self.out), nat.ptr(self.mu) if self.m else None,
-                                 nat.ptr(self.var) if self.m else None, s), "gpk_finalize")
+                                 nat.ptr(y), y_bstride, nat.ptr(self._W), s), "gpk_assemble")
+        nat.check(L.gpk_potrf_aug(ctypes.byref(lay), nat.ptr(self._W), nat.ptr(self._Winv),
+                                  nat.ptr(self._info), s), "gpk_potrf_aug")
+        nat.check(L.gpk_finalize(ctypes.byref(lay), nat.ptr(self._W), nat.ptr(self._info),
+                                 nat.ptr(self._out), nat.ptr(self._mu), nat.ptr(self._var), s), "gpk_finalize")
         self.kd = kd
         self.done = True
         return self
@@ -492,13 +546,13 @@ class AugmentedFactorization:
         return self.W[b * lay.w_batch_stride:(b + 1) * lay.w_batch_stride].view(lay.p, lay.ld)
 
     def nlml(self) -> torch.Tensor:
-        return self.out.view(self.batch, 4)[:, 0]
+        return self.results("nlml")[0]
 
     def unsettled_results(self):
-        """(-LML, info) device views WITHOUT settling a pending persistent run (no host synchronisation): for callers
-        that pipeline runs and only forward the values on the device -- a wait that timed out shows as info = -1
-        there, and the run is not re-done.  Everyone else reads nlml() / info."""
-        return self._out.view(self.batch, 4)[:, 0], self._info
+        """(-LML, info) device views WITHOUT settling a pending persistent run (:meth:`results`, settle=False).
+        Everyone who does not pipeline runs reads nlml() / info."""
+        f, _, info = self.results("nlml", settle=False)
+        return f, info
 
     def fit(self) -> torch.Tensor:
         return self.out.view(self.batch, 4)[:, 1]
@@ -506,36 +560,41 @@ class AugmentedFactorization:
     def logdet(self) -> torch.Tensor:
         return self.out.view(self.batch, 4)[:, 2]
 
+    def _counts(self, b: int):
+        """(training points, extra rows) of member b: what the size-aware read-outs slice by (ragged batches: the
+        member's own counts)."""
+        return self.n, self.m
+
     def cholesky(self, b: int = 0) -> torch.Tensor:
-        """L (lower, [n, n], p_dtype)."""
-        return torch.tril(self.w(b)[:self.n, :self.n])
+        """L (lower, [n_b, n_b], p_dtype)."""
+        nb, _ = self._counts(b)
+        return torch.tril(self.w(b)[:nb, :nb])
 
     def z(self, b: int = 0) -> torch.Tensor:
-        lay = self.layout
-        return self.w(b)[lay.y_row, :self.n]
+        return self.w(b)[self.layout.y_row, :self._counts(b)[0]]
 
     def extra_rows(self, b: int = 0) -> torch.Tensor:
-        """Rows n_pad .. n_pad+m-1 restricted to the first n columns: V^T = Ks^T L^-T (or E L^-T)."""
-        lay = self.layout
-        return self.w(b)[lay.n_pad:lay.n_pad + self.m, :self.n]
+        """Rows n_pad .. n_pad+m_b-1 restricted to the first n_b columns: V^T = Ks^T L^-T (or E L^-T)."""
+        lay, (nb, mb) = self.layout, self._counts(b)
+        return self.w(b)[lay.n_pad:lay.n_pad + mb, :nb]
 
     def corner(self, b: int = 0) -> torch.Tensor:
-        """Symmetrised m x m Schur complement: Kss - V^T V (or -E K^-1 E^T)."""
-        lay = self.layout
-        c = self.w(b)[lay.n_pad:lay.n_pad + self.m, lay.n_pad:lay.n_pad + self.m]
-        lo = torch.tril(c)
-        return lo + torch.tril(c, -1).transpose(0, 1)
+        """Symmetrised m_b x m_b Schur complement: Kss - V^T V (or -E K^-1 E^T)."""
+        lay, (_, mb) = self.layout, self._counts(b)
+        c = self.w(b)[lay.n_pad:lay.n_pad + mb, lay.n_pad:lay.n_pad + mb]
+        return torch.tril(c) + torch.tril(c, -1).transpose(0, 1)
 
     def posterior_mu(self, b: int = 0) -> torch.Tensor:
-        return self.mu[b * self.m:(b + 1) * self.m]
+        return self.mu[b * self.m:b * self.m + self._counts(b)[1]]
 
     def posterior_var_diag(self, b: int = 0) -> torch.Tensor:
-        return self.var[b * self.m:(b + 1) * self.m]
+        return self.var[b * self.m:b * self.m + self._counts(b)[1]]
 
     def alphas(self) -> torch.Tensor:
         """[batch, n]: alpha_b = L_b^-T z_b = (K_b + noise I)^-1 y_b for every member from ONE batched
-        backward solve (gpk_trsv), computed once per run and kept until the next one."""
-        if getattr(self, "_alphas", None) is None:
+        backward solve (gpk_trsv; a ragged member's padding rows carry z = 0), computed once per run and kept until
+        the next one."""
+        if self._alphas is None:
             lay = self.layout
             x = torch.zeros((self.batch, lay.n_pad), dtype=torch.float64, device=self.W.device)
             x[:, :self.n] = self.W.view(self.batch, lay.p, lay.ld)[:, lay.y_row, :self.n]
@@ -550,22 +609,19 @@ class AugmentedFactorization:
 
     # -- held-out MSE and its gradient (gpk_mse_backward / gpk_mse_grad) ------------------------
     def _mse_buffers(self, kd):
-        """(out [B * 4], grad [B, n_hyp + 1], work) of the MSE pass: the workspace is kept between calls, the two
-        result buffers are the caching allocator's per evaluation (earlier views stay valid, as _fresh_out)."""
+        """(out [B * 4], grad [B, n_hyp + 1], work) of the MSE pass, recorded as the "mse" results."""
         nat.require_mse_grad(self.L)
         if self.m < 1:
             raise ValueError("the MSE needs test points: this factorisation was planned with m = 0")
         if self.code != nat.GPK_F64:
             raise NotImplementedError("the MSE gradient is fp64 only")
-        dev = self._W.device
         need = int(self.L.gpk_mse_grad_workspace_bytes(ctypes.byref(kd), ctypes.byref(self.layout)))
         if need == 0:
             raise ValueError("the kernel program is not valid for dimension %d" % self.d)
-        if self._mse_work is None or self._mse_work.numel() * 8 < need:
-            self._mse_work = torch.empty(need // 8, dtype=torch.float64, device=dev)
-        self._mse_out = torch.empty(self.batch * 4, dtype=torch.float64, device=dev)
-        self._mse_grad = torch.empty((self.batch, kd.n_hyp + 1), dtype=torch.float64, device=dev)
-        return self._mse_out, self._mse_grad, self._mse_work
+        work = self._workspace(need)
+        out, grad = self._new(self.batch * 4), self._new(self.batch, kd.n_hyp + 1)
+        self._record("mse", out, grad)
+        return out, grad, work
 
     def _ragged_counts(self):
         """(n_dev, m_dev) pointers of a ragged batch; (None, None) here."""
@@ -581,7 +637,7 @@ class AugmentedFactorization:
             raise RuntimeError("run(..., Xs=...) with test points first")
         kd, hyp, hyp_stride, X, x_bstride, Xs, xs_bstride = ops
         out, grad, work = self._mse_buffers(kd)
-        dev = self._W.device
+        dev = self._dev
         _check_operand("y_test", ys, ys_bstride, self.m, self.batch, dev)
         n_ptr, m_ptr = self._ragged_counts()
         nat.check(self.L.gpk_mse_backward(
@@ -589,7 +645,7 @@ class AugmentedFactorization:
             nat.ptr(Xs), xs_bstride, nat.ptr(ys), ys_bstride, n_ptr, m_ptr, nat.ptr(self.W), nat.ptr(self.Winv),
             nat.ptr(self.info), nat.ptr(out), nat.ptr(grad), nat.ptr(work), work.numel() * 8,
             nat.stream_handle(dev)), "gpk_mse_backward")
-        self._keep_mse = ys
+        self._keep = (self._keep[0], ys)
         return out.view(self.batch, 4)[:, 0], grad
 
     def run_mse(self, kd: nat.GpkKdesc, hyp: torch.Tensor, hyp_stride: int, noise: torch.Tensor, noise_stride: int,
@@ -598,24 +654,16 @@ class AugmentedFactorization:
         """K build + factorisation + MSE value and gradient as one call (gpk_mse_grad); asynchronous, a persistent
         run is verified at the first read (:meth:`mse`, :meth:`mse_grad`, info).  ``unsettled_mse()`` gives the views
         without that."""
-        args = (kd, hyp, hyp_stride, noise, noise_stride, X, x_bstride, y, y_bstride, Xs, xs_bstride, ys, ys_bstride)
-        self._pending = None
-        self._run_mse_once(*args)
-        self._defer_verify(lambda: self._run_mse_once(*args))
-        return self
+        return self._enqueue(self._run_mse_once, kd, hyp, hyp_stride, noise, noise_stride, X, x_bstride, y, y_bstride,
+                             Xs, xs_bstride, ys, ys_bstride)
 
     def _run_mse_once(self, kd, hyp, hyp_stride, noise, noise_stride, X, x_bstride, y, y_bstride, Xs, xs_bstride,
                       ys, ys_bstride):
-        B, n, m, d = self.batch, self.n, self.m, self.d
-        dev = self._W.device
+        dev = self._dev
         self._alphas = None
         out, grad, work = self._mse_buffers(kd)
-        _check_operand("hyper_parameter", hyp, hyp_stride, kd.n_hyp, B, dev)
-        _check_operand("noise", noise, noise_stride, 1, B, dev)
-        _check_operand("X", X, x_bstride, n * d, B, dev)
-        _check_operand("y", y, y_bstride, n, B, dev)
-        _check_operand("X_test", Xs, xs_bstride, m * d, B, dev)
-        _check_operand("y_test", ys, ys_bstride, m, B, dev)
+        self._check_operands(kd.n_hyp, hyp, hyp_stride, noise, noise_stride, X, x_bstride, y, y_bstride,
+                             X_test=(Xs, xs_bstride), y_test=(ys, ys_bstride))
         n_ptr, m_ptr = self._ragged_counts()
         nat.check(self.L.gpk_mse_grad(
             ctypes.byref(kd), ctypes.byref(self.layout), nat.ptr(hyp), hyp_stride, nat.ptr(noise), noise_stride,
@@ -623,28 +671,22 @@ class AugmentedFactorization:
             n_ptr, m_ptr, nat.ptr(self._W), nat.ptr(self._Winv), nat.ptr(self._info), nat.ptr(out), nat.ptr(grad),
             nat.ptr(work), work.numel() * 8, nat.stream_handle(dev)), "gpk_mse_grad")
         self._mse_operands = (kd, hyp, hyp_stride, X, x_bstride, Xs, xs_bstride)
-        self._keep_mse = (noise, y, ys)
+        self._keep = ((noise, y, ys), None)
         self.kd = kd
         self.done = True
         return self
 
     def mse(self) -> torch.Tensor:
         """[batch] mean squared errors of the last run_mse / mse_gradient (+inf where info != 0)."""
-        self._settle()
-        if self._mse_out is None:
-            raise RuntimeError("run_mse(...) or mse_gradient(...) first")
-        return self._mse_out.view(self.batch, 4)[:, 0]
+        return self.results("mse")[0]
 
     def mse_grad(self) -> torch.Tensor:
         """[batch, n_hyp + 1] fp64: d mse / d hyp (DFS order), then d mse / d noise."""
-        self._settle()
-        if self._mse_grad is None:
-            raise RuntimeError("run_mse(...) or mse_gradient(...) first")
-        return self._mse_grad
+        return self.results("mse")[1]
 
     def unsettled_mse(self):
         """(mse, gradient, info) device views WITHOUT settling a pending persistent run (see unsettled_results)."""
-        return self._mse_out.view(self.batch, 4)[:, 0], self._mse_grad, self._info
+        return self.results("mse", settle=False)
 
     def check_info(self):
         """Raise CholeskyError if any batch member failed (synchronises)."""
@@ -659,7 +701,25 @@ class AugmentedFactorization:
             raise CholeskyError(int(info[bad[0]]))
 
 
-class InverseFactorization(AugmentedFactorization):
+class _IdentityReadout:
+    """Read-outs of an identity-augmented factorisation (extra rows e_t): the extra rows hold L^-T, the corner -K^-1
+    and the corner's y row -alpha^T (include/gpk.h), each sliced to the member's own size."""
+
+    def k_inv(self, b: int = 0) -> torch.Tensor:
+        """(K_b + noise I)^-1 [n_b, n_b], symmetrised from the corner's lower triangle."""
+        return -self.corner(b)
+
+    def l_inv(self, b: int = 0) -> torch.Tensor:
+        """L_b^-1 (lower): the transpose of the extra rows, which hold L_b^-T."""
+        return torch.triu(self.extra_rows(b)).transpose(0, 1)
+
+    def alpha(self, b: int = 0) -> torch.Tensor:
+        """alpha_b [n_b], read from the corner's y row."""
+        lay = self.layout
+        return -self.w(b)[lay.y_row, lay.n_pad:lay.n_pad + self._counts(b)[0]].to(torch.float64)
+
+
+class InverseFactorization(_IdentityReadout, AugmentedFactorization):
     """Factorisation of the augmented matrix with identity extra rows (m = n), optionally followed
     by the -LML gradient (``gpk_nlml_grad``).
 
@@ -672,45 +732,31 @@ class InverseFactorization(AugmentedFactorization):
 
     def __init__(self, n: int, d: int, batch: int = 1, dtype=None):
         super().__init__(n, d, n, batch, dtype)
-        self.grad = None
-        self.work = None
 
     def run(self, kd: nat.GpkKdesc, hyp: torch.Tensor, hyp_stride: int, noise: torch.Tensor,
             noise_stride: int, X: torch.Tensor, x_bstride: int, y: torch.Tensor, y_bstride: int,
             gradient: bool = True, **unused):
         """Enqueue the identity-augmented factorisation (+ gradient); single evaluations take the persistent
         launch like the value path and are verified at the first read (CHAIN_VERIFY)."""
-        args = (kd, hyp, hyp_stride, noise, noise_stride, X, x_bstride, y, y_bstride, gradient)
-        self._pending = None
-        self._run_inverse(*args)
-        self._defer_verify(lambda: self._run_inverse(*args))
-        return self
+        return self._enqueue(self._run_inverse, kd, hyp, hyp_stride, noise, noise_stride, X, x_bstride, y, y_bstride,
+                             gradient)
 
     def _run_inverse(self, kd, hyp, hyp_stride, noise, noise_stride, X, x_bstride, y, y_bstride, gradient):
-        lay = self.layout
-        B, n, d = self.batch, self.n, self.d
-        dev = self.W.device
+        lay, L = self.layout, self.L
         self._alphas = None
-        self._fresh_out()
-        _check_operand("hyper_parameter", hyp, hyp_stride, kd.n_hyp, B, dev)
-        _check_operand("noise", noise, noise_stride, 1, B, dev)
-        _check_operand("X", X, x_bstride, n * d, B, dev)
-        _check_operand("y", y, y_bstride, n, B, dev)
-        L = self.L
-        grad_ptr = work_ptr = None
-        work_bytes = 0
+        self._out = self._new(self.batch * 4)
+        grad = self._new(self.batch, kd.n_hyp + 1) if gradient else None
+        self._record("nlml", self._out, grad)
+        self._check_operands(kd.n_hyp, hyp, hyp_stride, noise, noise_stride, X, x_bstride, y, y_bstride)
+        work, work_bytes = None, 0
         if gradient:
             work_bytes = int(L.gpk_grad_workspace_bytes(ctypes.byref(kd), ctypes.byref(lay)))
-            if self.work is None or self.work.numel() * 8 < work_bytes:
-                self.work = torch.empty(max(1, work_bytes // 8), dtype=torch.float64, device=dev)
-            self.grad = torch.empty((B, kd.n_hyp + 1), dtype=torch.float64, device=dev)
-            grad_ptr, work_ptr = nat.ptr(self.grad), nat.ptr(self.work)
-        else:
-            self.grad = None
+            work = self._workspace(work_bytes)
         nat.check(L.gpk_nlml_grad(ctypes.byref(kd), ctypes.byref(lay), nat.ptr(hyp), hyp_stride,
                                   nat.ptr(noise), noise_stride, nat.ptr(X), x_bstride, nat.ptr(y), y_bstride,
-                                  nat.ptr(self.W), nat.ptr(self.Winv), nat.ptr(self.info), nat.ptr(self.out),
-                                  grad_ptr, work_ptr, work_bytes, nat.stream_handle(dev)), "gpk_nlml_grad")
+                                  nat.ptr(self._W), nat.ptr(self._Winv), nat.ptr(self._info), nat.ptr(self._out),
+                                  nat.ptr(grad), nat.ptr(work), work_bytes, nat.stream_handle(self._dev)),
+                  "gpk_nlml_grad")
         self._loo_operands = (kd, hyp, hyp_stride, X, x_bstride, y, y_bstride)   # (what loo() needs of this run)
         self.kd = kd
         self.done = True
@@ -718,23 +764,21 @@ class InverseFactorization(AugmentedFactorization):
 
     # -- leave-one-out cross-validation (gpk_loo_backward / gpk_loo_grad) ------------------------
     def _loo_buffers(self, kd, gradient: bool):
-        """The workspace is kept between calls; the result buffers (out [B * 4], mu and var [B, n], grad
-        [B, n_hyp + 1]) are the caching allocator's per evaluation, so earlier views stay valid (as _fresh_out)."""
+        """(out [B * 4], mu [B, n], var [B, n], grad [B, n_hyp + 1] or None, work) of the LOO pass, recorded as the
+        "loo" results."""
         nat.require_loo(self.L)
         if self.code != nat.GPK_F64:
             raise NotImplementedError("leave-one-out is fp64 only")
-        dev = self._W.device
         need = int(self.L.gpk_loo_workspace_bytes(ctypes.byref(kd), ctypes.byref(self.layout)))
         if need == 0:
             raise ValueError("the kernel program is not valid for dimension %d" % self.d)
-        if getattr(self, "_loo_work", None) is None or self._loo_work.numel() * 8 < need:
-            self._loo_work = torch.empty(need // 8, dtype=torch.float64, device=dev)
-        self._loo_out = torch.empty(self.batch * 4, dtype=torch.float64, device=dev)
-        self._loo_mu = torch.empty((self.batch, self.n), dtype=torch.float64, device=dev)
-        self._loo_var = torch.empty((self.batch, self.n), dtype=torch.float64, device=dev)
-        self._loo_grad = (torch.empty((self.batch, kd.n_hyp + 1), dtype=torch.float64, device=dev)
-                          if gradient else None)
-        return self._loo_work
+        work = self._workspace(need)
+        B, n = self.batch, self.n
+        self._loo_out = out = self._new(B * 4)
+        mu, var = self._new(B, n), self._new(B, n)
+        grad = self._new(B, kd.n_hyp + 1) if gradient else None
+        self._record("loo", out, grad, mu, var)
+        return out, mu, var, grad, work
 
     def loo(self, loss, gradient: bool = True):
         """The leave-one-out pass alone on the last :meth:`run` (gpk_loo_backward; W is only read):
@@ -742,19 +786,18 @@ class InverseFactorization(AugmentedFactorization):
         synchronisation (a pending persistent run is settled first, like every read of W).  ``loss``:
         nat.LOO_LPD (minus the LOO log predictive density) or nat.LOO_MSE; f is +inf, the rest NaN where info != 0.
         mu is in the units of the y that was factored."""
-        ops = getattr(self, "_loo_operands", None) if self.done else None
+        ops = self._loo_operands if self.done else None
         if ops is None:
             raise RuntimeError("run(...) first")
         loss = nat.loo_loss_code(loss)
         kd, hyp, hyp_stride, X, x_bstride, y, y_bstride = ops
-        work = self._loo_buffers(kd, gradient)
-        dev = self._W.device
+        self._settle()   # (before the buffers: a re-run of a timed-out run_loo records its own)
+        out, mu, var, grad, work = self._loo_buffers(kd, gradient)
         nat.check(self.L.gpk_loo_backward(
             loss, ctypes.byref(kd), ctypes.byref(self.layout), nat.ptr(hyp), hyp_stride, nat.ptr(X), x_bstride,
-            nat.ptr(y), y_bstride, None, nat.ptr(self.W), nat.ptr(self.info), nat.ptr(self._loo_out),
-            nat.ptr(self._loo_mu), nat.ptr(self._loo_var), nat.ptr(self._loo_grad), nat.ptr(work), work.numel() * 8,
-            nat.stream_handle(dev)), "gpk_loo_backward")
-        return self._loo_out.view(self.batch, 4)[:, 0], self._loo_grad, self._loo_mu, self._loo_var
+            nat.ptr(y), y_bstride, None, nat.ptr(self.W), nat.ptr(self.info), nat.ptr(out), nat.ptr(mu), nat.ptr(var),
+            nat.ptr(grad), nat.ptr(work), work.numel() * 8, nat.stream_handle(self._dev)), "gpk_loo_backward")
+        return self._views("loo")
 
     def run_loo(self, loss, kd: nat.GpkKdesc, hyp: torch.Tensor, hyp_stride: int, noise: torch.Tensor,
                 noise_stride: int, X: torch.Tensor, x_bstride: int, y: torch.Tensor, y_bstride: int,
@@ -762,30 +805,21 @@ class InverseFactorization(AugmentedFactorization):
         """K build + identity-augmented factorisation + the leave-one-out pass as one call (gpk_loo_grad);
         asynchronous, a persistent run is verified at the first read (:meth:`loo_results`, info).
         ``unsettled_loo()`` gives the views without that."""
-        args = (nat.loo_loss_code(loss), kd, hyp, hyp_stride, noise, noise_stride, X, x_bstride, y, y_bstride,
-                gradient)
-        self._pending = None
-        self._run_loo_once(*args)
-        self._defer_verify(lambda: self._run_loo_once(*args))
-        return self
+        return self._enqueue(self._run_loo_once, nat.loo_loss_code(loss), kd, hyp, hyp_stride, noise, noise_stride,
+                             X, x_bstride, y, y_bstride, gradient)
 
     def _run_loo_once(self, loss, kd, hyp, hyp_stride, noise, noise_stride, X, x_bstride, y, y_bstride, gradient):
-        B, n, d = self.batch, self.n, self.d
-        dev = self._W.device
         self._alphas = None
-        self.grad = None
-        work = self._loo_buffers(kd, gradient)
-        _check_operand("hyper_parameter", hyp, hyp_stride, kd.n_hyp, B, dev)
-        _check_operand("noise", noise, noise_stride, 1, B, dev)
-        _check_operand("X", X, x_bstride, n * d, B, dev)
-        _check_operand("y", y, y_bstride, n, B, dev)
+        self._record("nlml", self._out)   # (no -LML gradient of this run)
+        out, mu, var, grad, work = self._loo_buffers(kd, gradient)
+        self._check_operands(kd.n_hyp, hyp, hyp_stride, noise, noise_stride, X, x_bstride, y, y_bstride)
         nat.check(self.L.gpk_loo_grad(
             loss, ctypes.byref(kd), ctypes.byref(self.layout), nat.ptr(hyp), hyp_stride, nat.ptr(noise), noise_stride,
             nat.ptr(X), x_bstride, nat.ptr(y), y_bstride, None, nat.ptr(self._W), nat.ptr(self._Winv),
-            nat.ptr(self._info), nat.ptr(self._loo_out), nat.ptr(self._loo_mu), nat.ptr(self._loo_var),
-            nat.ptr(self._loo_grad), nat.ptr(work), work.numel() * 8, nat.stream_handle(dev)), "gpk_loo_grad")
+            nat.ptr(self._info), nat.ptr(out), nat.ptr(mu), nat.ptr(var), nat.ptr(grad), nat.ptr(work),
+            work.numel() * 8, nat.stream_handle(self._dev)), "gpk_loo_grad")
         self._loo_operands = (kd, hyp, hyp_stride, X, x_bstride, y, y_bstride)
-        self._keep_loo = noise
+        self._keep = (noise, None)
         self.kd = kd
         self.done = True
         return self
@@ -793,33 +827,19 @@ class InverseFactorization(AugmentedFactorization):
     def loo_results(self):
         """(f [B], grad [B, n_hyp + 1] or None, mu [B, n], var [B, n]) of the last run_loo / loo (settles a pending
         persistent run)."""
-        self._settle()
-        if getattr(self, "_loo_out", None) is None:
-            raise RuntimeError("run_loo(...) or loo(...) first")
-        return self._loo_out.view(self.batch, 4)[:, 0], self._loo_grad, self._loo_mu, self._loo_var
+        self.results("loo")
+        return self._views("loo")
 
     def unsettled_loo(self):
         """(f, gradient, info) device views WITHOUT settling a pending persistent run (see unsettled_results)."""
-        return self._loo_out.view(self.batch, 4)[:, 0], self._loo_grad, self._info
+        return self.results("loo", settle=False)
 
     def gradient(self) -> torch.Tensor:
         """[batch, n_hyp + 1] fp64: d(-LML)/d hyp (DFS order), then d(-LML)/d noise."""
-        self._settle()
-        if self.grad is None:
+        g = self.results("nlml")[1]
+        if g is None:
             raise RuntimeError("run(..., gradient=True) first")
-        return self.grad
-
-    def k_inv(self, b: int = 0) -> torch.Tensor:
-        """(K + noise I)^-1, symmetrised from the corner's lower triangle."""
-        return -self.corner(b)
-
-    def l_inv(self, b: int = 0) -> torch.Tensor:
-        """L^-1 (lower): the transpose of the extra rows, which hold L^-T."""
-        return torch.triu(self.extra_rows(b)).transpose(0, 1)
-
-    def alpha(self, b: int = 0) -> torch.Tensor:
-        lay = self.layout
-        return -self.w(b)[lay.y_row, lay.n_pad:lay.n_pad + self.n].to(torch.float64)
+        return g
 
     def neg_alpha_rows(self) -> torch.Tensor:
         """[batch, n] view of the -alpha rows inside W (element y_row * ld + n_pad of every member, batch stride
@@ -862,48 +882,27 @@ class RaggedFactorization(AugmentedFactorization):
         self.n_dev = torch.tensor(sizes, dtype=torch.int64, device=dev)
         self.m_dev = torch.tensor(tsz, dtype=torch.int64, device=dev)
 
+    def _counts(self, b: int):
+        return self.sizes[b], self.test_sizes[b]
+
     def run(self, members: Sequence, noise) -> "RaggedFactorization":
         """members[b] = (kdesc, hyp [n_hyp] fp64, X_b [n_b, d], y_b [n_b], Xs_b [m_b, d] or None);
         noise: rank-0 or one value per member."""
         self._pending = None
         B, n, m, d = self.batch, self.n, self.m, self.d
         self._alphas = None
-        if len(members) != B:
-            raise ValueError("expected %d members, got %d" % (B, len(members)))
-        dev = self.W.device
-        X = torch.zeros((B, n, d), dtype=torch.float64, device=dev)
-        y = torch.zeros((B, n), dtype=torch.float64, device=dev)
-        Xs = torch.zeros((B, max(m, 1), d), dtype=torch.float64, device=dev)
-        hyp = torch.zeros((B, nat.MAX_HYP), dtype=torch.float64, device=dev)
-        kds = []
-        for b, (kd, h, xb, yb, xsb) in enumerate(members):
-            nb, mb = self.sizes[b], self.test_sizes[b]
-            if tuple(xb.shape) != (nb, d) or yb.numel() != nb:
-                raise ValueError("member %d: X must be [%d, %d] and y hold %d values" % (b, nb, d, nb))
-            if h.numel() != kd.n_hyp:
-                raise ValueError("member %d: %d hyperparameters, kernel expects %d" % (b, h.numel(), kd.n_hyp))
-            X[b, :nb] = xb
-            y[b, :nb] = yb.reshape(-1)
-            if mb:
-                if xsb is None or tuple(xsb.shape) != (mb, d):
-                    raise ValueError("member %d: X_test must be [%d, %d]" % (b, mb, d))
-                Xs[b, :mb] = xsb
-            hyp[b, :kd.n_hyp] = h
-            kds.append(kd)
-        nz = noise if isinstance(noise, torch.Tensor) else torch.as_tensor(noise, dtype=torch.float64)
-        nz = nz.detach().to(device=dev, dtype=torch.float64).reshape(-1)
-        nz = (nz.expand(B) if nz.numel() == 1 else nz).contiguous()
-        if nz.numel() != B:
-            raise ValueError("noise must be rank-0 or hold one value per member")
+        kds, hyp, nz, X, y, Xs = _pack_members(self, members, noise, self.test_sizes)
+        dev = self._dev
         L, s = self.L, nat.stream_handle(dev)
         lay = self.layout
-        self.info.zero_()
+        self._info.zero_()
         mptr = nat.ptr(self.m_dev) if m else None
         xs_ptr = nat.ptr(Xs) if m else None
-        if all(bytes(k) == bytes(kds[0]) for k in kds):
+        same = all(bytes(k) == bytes(kds[0]) for k in kds)
+        if same:
             nat.check(L.gpk_assemble_ragged(ctypes.byref(kds[0]), ctypes.byref(lay), nat.ptr(hyp), nat.MAX_HYP,
                                             nat.ptr(nz), 1, nat.ptr(X), n * d, xs_ptr, max(m, 1) * d,
-                                            nat.ptr(y), n, nat.ptr(self.n_dev), mptr, nat.ptr(self.W), s),
+                                            nat.ptr(y), n, nat.ptr(self.n_dev), mptr, nat.ptr(self._W), s),
                       "gpk_assemble_ragged")
         else:
             one = nat.plan(self.code, 1, n, m, d)   # same p / ld as the batched layout
@@ -913,16 +912,15 @@ class RaggedFactorization(AugmentedFactorization):
                     _offset_ptr(nz, b), 0, _offset_ptr(X, b * n * d), 0,
                     _offset_ptr(Xs, b * max(m, 1) * d) if m else None, 0, _offset_ptr(y, b * n), 0,
                     _offset_ptr(self.n_dev, b), _offset_ptr(self.m_dev, b) if m else None,
-                    _offset_ptr(self.W, b * lay.w_batch_stride), s), "gpk_assemble_ragged")
-        nat.check(L.gpk_potrf_aug_ragged(ctypes.byref(lay), nat.ptr(self.W), nat.ptr(self.Winv),
-                                         nat.ptr(self.info), nat.ptr(self.n_dev), mptr, s), "gpk_potrf_aug_ragged")
-        nat.check(L.gpk_finalize_ragged(ctypes.byref(lay), nat.ptr(self.W), nat.ptr(self.info),
-                                        nat.ptr(self.n_dev), nat.ptr(self.out),
-                                        nat.ptr(self.mu) if m else None, nat.ptr(self.var) if m else None, s),
+                    _offset_ptr(self._W, b * lay.w_batch_stride), s), "gpk_assemble_ragged")
+        nat.check(L.gpk_potrf_aug_ragged(ctypes.byref(lay), nat.ptr(self._W), nat.ptr(self._Winv),
+                                         nat.ptr(self._info), nat.ptr(self.n_dev), mptr, s), "gpk_potrf_aug_ragged")
+        nat.check(L.gpk_finalize_ragged(ctypes.byref(lay), nat.ptr(self._W), nat.ptr(self._info),
+                                        nat.ptr(self.n_dev), nat.ptr(self._out),
+                                        nat.ptr(self._mu) if m else None, nat.ptr(self._var) if m else None, s),
                   "gpk_finalize_ragged")
-        self._keep = (X, y, Xs, hyp, nz)  # operands stay alive until the stream has consumed them
+        self._keep = ((X, y, Xs, hyp, nz), None)
         # (what mse_gradient needs of this run: one program for every member)
-        same = all(bytes(k) == bytes(kds[0]) for k in kds)
         self._mse_operands = (kds[0], hyp, nat.MAX_HYP, X, n * d, Xs, max(m, 1) * d) if same and m else None
         self.kd = kds
         self.done = True
@@ -940,7 +938,7 @@ class RaggedFactorization(AugmentedFactorization):
         if isinstance(ys, (list, tuple)):
             if len(ys) != self.batch:
                 raise ValueError("expected %d test-target vectors, got %d" % (self.batch, len(ys)))
-            packed = torch.zeros((self.batch, self.m), dtype=torch.float64, device=self._W.device)
+            packed = torch.zeros((self.batch, self.m), dtype=torch.float64, device=self._dev)
             for b, v in enumerate(ys):
                 if v.numel() != self.test_sizes[b]:
                     raise ValueError("member %d: y_test must hold %d values" % (b, self.test_sizes[b]))
@@ -961,43 +959,46 @@ class RaggedFactorization(AugmentedFactorization):
         self.kd = [kd] * self.batch
         return self
 
-    # -- per-member read-out ------------------------------------------------------------------
-    def cholesky(self, b: int = 0) -> torch.Tensor:
-        nb = self.sizes[b]
-        return torch.tril(self.w(b)[:nb, :nb])
-
-    def z(self, b: int = 0) -> torch.Tensor:
-        return self.w(b)[self.layout.y_row, :self.sizes[b]]
-
-    def extra_rows(self, b: int = 0) -> torch.Tensor:
-        lay = self.layout
-        return self.w(b)[lay.n_pad:lay.n_pad + self.test_sizes[b], :self.sizes[b]]
-
-    def corner(self, b: int = 0) -> torch.Tensor:
-        lay, mb = self.layout, self.test_sizes[b]
-        c = self.w(b)[lay.n_pad:lay.n_pad + mb, lay.n_pad:lay.n_pad + mb]
-        return torch.tril(c) + torch.tril(c, -1).transpose(0, 1)
-
-    def posterior_mu(self, b: int = 0) -> torch.Tensor:
-        return self.mu[b * self.m:b * self.m + self.test_sizes[b]]
-
-    def posterior_var_diag(self, b: int = 0) -> torch.Tensor:
-        return self.var[b * self.m:b * self.m + self.test_sizes[b]]
-
     def alphas(self) -> List[torch.Tensor]:
-        """alpha_b = L_b^-T z_b for every member: one batched backward solve (gpk_trsv; a member's
-        padding rows carry z = 0), computed once per run."""
-        if getattr(self, "_alphas", None) is None:
-            lay = self.layout
-            x = torch.zeros((self.batch, lay.n_pad), dtype=torch.float64, device=self.W.device)
-            x[:, :self.n] = self.W.view(self.batch, lay.p, lay.ld)[:, lay.y_row, :self.n]
-            nat.check(self.L.gpk_trsv(ctypes.byref(lay), 1, nat.ptr(self.W), nat.ptr(self.Winv),
-                                      nat.ptr(x), nat.stream_handle(self.W.device)), "gpk_trsv")
-            self._alphas = [x[b, :self.sizes[b]] for b in range(self.batch)]
-        return self._alphas
+        """alpha_b [n_b] for every member (one batched backward solve, see AugmentedFactorization.alphas)."""
+        rows = super().alphas()
+        return [rows[b, :self.sizes[b]] for b in range(self.batch)]
 
-    def alpha(self, b: int = 0) -> torch.Tensor:
-        return self.alphas()[b]
+
+def _pack_members(f, members: Sequence, noise, test_sizes=None):
+    """(kds, hyp [B, MAX_HYP], noise [B], X [B, n, d], y [B, n], Xs [B, max(m, 1), d] or None) of a ragged batch on
+    the device, zero-filled past each member's counts.  members[b] = (kdesc, hyp, X_b, y_b[, Xs_b]); ``noise``
+    rank-0 or one value per member; ``test_sizes``: the members' test counts where they carry test points."""
+    B, n, d = f.batch, f.n, f.d
+    if len(members) != B:
+        raise ValueError("expected %d members, got %d" % (B, len(members)))
+    dev = f._dev
+    X = torch.zeros((B, n, d), dtype=torch.float64, device=dev)
+    y = torch.zeros((B, n), dtype=torch.float64, device=dev)
+    Xs = torch.zeros((B, max(f.m, 1), d), dtype=torch.float64, device=dev) if test_sizes is not None else None
+    hyp = torch.zeros((B, nat.MAX_HYP), dtype=torch.float64, device=dev)
+    kds = []
+    for b, (kd, h, xb, yb, *xsb) in enumerate(members):
+        nb = f.sizes[b]
+        if tuple(xb.shape) != (nb, d) or yb.numel() != nb:
+            raise ValueError("member %d: X must be [%d, %d] and y hold %d values" % (b, nb, d, nb))
+        if h.numel() != kd.n_hyp:
+            raise ValueError("member %d: %d hyperparameters, kernel expects %d" % (b, h.numel(), kd.n_hyp))
+        X[b, :nb] = xb.detach()
+        y[b, :nb] = yb.detach().reshape(-1)
+        if test_sizes is not None and test_sizes[b]:
+            mb = test_sizes[b]
+            if not xsb or xsb[0] is None or tuple(xsb[0].shape) != (mb, d):
+                raise ValueError("member %d: X_test must be [%d, %d]" % (b, mb, d))
+            Xs[b, :mb] = xsb[0].detach()
+        hyp[b, :kd.n_hyp] = h.detach().reshape(-1)
+        kds.append(kd)
+    nz = noise if isinstance(noise, torch.Tensor) else torch.as_tensor(noise, dtype=torch.float64)
+    nz = nz.detach().to(device=dev, dtype=torch.float64).reshape(-1)
+    nz = (nz.expand(B) if nz.numel() == 1 else nz).contiguous()
+    if nz.numel() != B:
+        raise ValueError("noise must be rank-0 or hold one value per member")
+    return kds, hyp, nz, X, y, Xs
 
 
 def program_runs(kds: Sequence) -> List[tuple]:
@@ -1011,7 +1012,7 @@ def program_runs(kds: Sequence) -> List[tuple]:
     return runs
 
 
-class RaggedInverseFactorization(AugmentedFactorization):
+class RaggedInverseFactorization(_IdentityReadout, AugmentedFactorization):
     """Identity-augmented factorisation (+ -LML gradient) of independent problems of DIFFERENT sizes: the sibling of
     :class:`RaggedFactorization` for what :class:`InverseFactorization` computes (gpk_assemble_inverse_ragged,
     gpk_potrf_aug_ragged_ex, gpk_finalize_ragged, gpk_grad_ragged).
@@ -1037,36 +1038,27 @@ class RaggedInverseFactorization(AugmentedFactorization):
         super().__init__(max(sizes), d, max(sizes), len(sizes), dtype)
         self.sizes = sizes
         self.n_dev = torch.tensor(sizes, dtype=torch.int64, device=self.W.device)
-        self.grad = None
-        self.work = None
+        self._grads = self._runs = self._packed = None
+
+    def _counts(self, b: int):
+        return self.sizes[b], self.sizes[b]
 
     def run(self, members: Sequence, noise, gradient: bool = True) -> "RaggedInverseFactorization":
         """members[b] = (kdesc, hyp [n_hyp] fp64, X_b [n_b, d], y_b [n_b]); noise: rank-0 or one value per member.
         Asynchronous; ``gradient()`` / ``nlml()`` are device tensors."""
-        B, n, d = self.batch, self.n, self.d
-        if len(members) != B:
-            raise ValueError("expected %d members, got %d" % (B, len(members)))
-        dev = self.W.device
-        X = torch.zeros((B, n, d), dtype=torch.float64, device=dev)
-        y = torch.zeros((B, n), dtype=torch.float64, device=dev)
-        hyp = torch.zeros((B, nat.MAX_HYP), dtype=torch.float64, device=dev)
-        kds = []
-        for b, (kd, h, xb, yb) in enumerate(members):
-            nb = self.sizes[b]
-            if tuple(xb.shape) != (nb, d) or yb.numel() != nb:
-                raise ValueError("member %d: X must be [%d, %d] and y hold %d values" % (b, nb, d, nb))
-            if h.numel() != kd.n_hyp:
-                raise ValueError("member %d: %d hyperparameters, kernel expects %d" % (b, h.numel(), kd.n_hyp))
-            X[b, :nb] = xb.detach()
-            y[b, :nb] = yb.detach().reshape(-1)
-            hyp[b, :kd.n_hyp] = h.detach().reshape(-1)
-            kds.append(kd)
-        nz = noise if isinstance(noise, torch.Tensor) else torch.as_tensor(noise, dtype=torch.float64)
-        nz = nz.detach().to(device=dev, dtype=torch.float64).reshape(-1)
-        nz = (nz.expand(B) if nz.numel() == 1 else nz).contiguous()
-        if nz.numel() != B:
-            raise ValueError("noise must be rank-0 or hold one value per member")
+        kds, hyp, nz, X, y, _ = _pack_members(self, members, noise)
         return self.run_packed(kds, hyp, nz, X, y, gradient)
+
+    def _program_runs(self, kds: Sequence) -> List[tuple]:
+        """(b0, b1, program, sub-layout) per run of :func:`program_runs`: the batch layout of the run's b1 - b0
+        members (same p / ld / strides as the whole batch's), to be used with pointers offset to member b0."""
+        lays = {self.batch: self.layout}
+        runs = []
+        for b0, b1 in program_runs(kds):
+            if b1 - b0 not in lays:
+                lays[b1 - b0] = nat.plan(self.code, b1 - b0, self.n, self.n, self.d)
+            runs.append((b0, b1, kds[b0], lays[b1 - b0]))
+        return runs
 
     def run_packed(self, kds: Sequence, hyp: torch.Tensor, noise: torch.Tensor, X: torch.Tensor, y: torch.Tensor,
                    gradient: bool = True) -> "RaggedInverseFactorization":
@@ -1075,27 +1067,17 @@ class RaggedInverseFactorization(AugmentedFactorization):
         self._pending = None
         self._alphas = None
         B, n, d = self.batch, self.n, self.d
-        dev = self.W.device
+        dev = self._dev
         if len(kds) != B:
             raise ValueError("expected %d programs, got %d" % (B, len(kds)))
-        _check_operand("hyper_parameter", hyp, nat.MAX_HYP, nat.MAX_HYP, B, dev)
-        _check_operand("noise", noise, 1, 1, B, dev)
-        _check_operand("X", X, n * d, n * d, B, dev)
-        _check_operand("y", y, n, n, B, dev)
+        self._check_operands(nat.MAX_HYP, hyp, nat.MAX_HYP, noise, 1, X, n * d, y, n)
         self._fresh_out()
         L, s, lay = self.L, nat.stream_handle(dev), self.layout
-        runs = program_runs(kds)
-        lays = {}
-
-        def sub_layout(count):   # same p / ld / strides as the batched layout
-            if count not in lays:
-                lays[count] = lay if count == B else nat.plan(self.code, count, n, n, d)
-            return lays[count]
-
-        self.info.zero_()
-        for b0, b1 in runs:
+        runs = self._program_runs(kds)
+        self._info.zero_()
+        for b0, b1, kd, sl in runs:
             nat.check(L.gpk_assemble_inverse_ragged(
-                ctypes.byref(kds[b0]), ctypes.byref(sub_layout(b1 - b0)), _offset_ptr(hyp, b0 * nat.MAX_HYP),
+                ctypes.byref(kd), ctypes.byref(sl), _offset_ptr(hyp, b0 * nat.MAX_HYP),
                 nat.MAX_HYP, _offset_ptr(noise, b0), 1, _offset_ptr(X, b0 * n * d), n * d, _offset_ptr(y, b0 * n), n,
                 _offset_ptr(self.n_dev, b0), _offset_ptr(self._W, b0 * lay.w_batch_stride), s),
                 "gpk_assemble_inverse_ragged")
@@ -1105,26 +1087,25 @@ class RaggedInverseFactorization(AugmentedFactorization):
         nat.check(L.gpk_finalize_ragged(ctypes.byref(lay), nat.ptr(self._W), nat.ptr(self._info),
                                         nat.ptr(self.n_dev), nat.ptr(self._out), None, None, s),
                   "gpk_finalize_ragged")
-        self.grad = self._grads = None
+        self._grads = None
         if gradient:
             # one workspace for every run (sized for the run that needs most; the runs follow each other on the stream)
-            need = max(int(L.gpk_grad_workspace_bytes(ctypes.byref(kds[b0]), ctypes.byref(sub_layout(b1 - b0))))
-                       for b0, b1 in runs)
-            if self.work is None or self.work.numel() * 8 < need:
-                self.work = torch.empty(max(1, need // 8), dtype=torch.float64, device=dev)
+            work = self._workspace(max(int(L.gpk_grad_workspace_bytes(ctypes.byref(kd), ctypes.byref(sl)))
+                                       for _, _, kd, sl in runs))
             self._grads = []
-            for b0, b1 in runs:
-                kd, sl = kds[b0], sub_layout(b1 - b0)
-                g = torch.empty((b1 - b0, kd.n_hyp + 1), dtype=torch.float64, device=dev)
+            for b0, b1, kd, sl in runs:
+                g = self._new(b1 - b0, kd.n_hyp + 1)
                 nat.check(L.gpk_grad_ragged(
                     ctypes.byref(kd), ctypes.byref(sl), _offset_ptr(hyp, b0 * nat.MAX_HYP), nat.MAX_HYP,
                     _offset_ptr(X, b0 * n * d), n * d, _offset_ptr(self.n_dev, b0),
                     _offset_ptr(self._W, b0 * lay.w_batch_stride), _offset_ptr(self._info, b0), nat.ptr(g),
-                    nat.ptr(self.work), self.work.numel() * 8, s), "gpk_grad_ragged")
+                    nat.ptr(work), work.numel() * 8, s), "gpk_grad_ragged")
                 self._grads.append(g)
-            self.grad = self._grads[0] if len(runs) == 1 else None
-            self._runs = runs
-        self._keep = (X, y, hyp, noise)  # operands stay alive until the stream has consumed them
+            if len(runs) == 1:   # (one program: the gradient of the whole batch is one tensor)
+                self._record("nlml", self._out, self._grads[0])
+        self._runs = runs
+        self._packed = (hyp, X, y)   # (what loo() needs of this run)
+        self._keep = ((X, y, hyp, noise), None)
         self.kd = list(kds)
         self.done = True
         return self
@@ -1142,32 +1123,24 @@ class RaggedInverseFactorization(AugmentedFactorization):
         if self.code != nat.GPK_F64:
             raise NotImplementedError("leave-one-out is fp64 only")
         loss = nat.loo_loss_code(loss)
-        X, y, hyp, _ = self._keep
-        kds = self.kd
+        hyp, X, y = self._packed
         B, n, d = self.batch, self.n, self.d
-        L, lay, dev = self.L, self.layout, self._W.device
-        s = nat.stream_handle(dev)
-        runs = program_runs(kds)
-        lays = {b1 - b0: (lay if b1 - b0 == B else nat.plan(self.code, b1 - b0, n, n, d)) for b0, b1 in runs}
-        need = max(int(L.gpk_loo_workspace_bytes(ctypes.byref(kds[b0]), ctypes.byref(lays[b1 - b0])))
-                   for b0, b1 in runs)
+        L, lay = self.L, self.layout
+        s = nat.stream_handle(self._dev)
+        need = max(int(L.gpk_loo_workspace_bytes(ctypes.byref(kd), ctypes.byref(sl))) for _, _, kd, sl in self._runs)
         if need == 0:
             raise ValueError("the kernel program is not valid for dimension %d" % d)
-        if getattr(self, "_loo_work", None) is None or self._loo_work.numel() * 8 < need:
-            self._loo_work = torch.empty(need // 8, dtype=torch.float64, device=dev)
-        out = torch.empty(B * 4, dtype=torch.float64, device=dev)
-        mu = torch.empty((B, n), dtype=torch.float64, device=dev)
-        var = torch.empty((B, n), dtype=torch.float64, device=dev)
+        work = self._workspace(need)
+        out, mu, var = self._new(B * 4), self._new(B, n), self._new(B, n)
         grads = [] if gradient else None
-        for b0, b1 in runs:
-            kd, sl = kds[b0], lays[b1 - b0]
-            g = torch.empty((b1 - b0, kd.n_hyp + 1), dtype=torch.float64, device=dev) if gradient else None
+        for b0, b1, kd, sl in self._runs:
+            g = self._new(b1 - b0, kd.n_hyp + 1) if gradient else None
             nat.check(L.gpk_loo_backward(
                 loss, ctypes.byref(kd), ctypes.byref(sl), _offset_ptr(hyp, b0 * nat.MAX_HYP), nat.MAX_HYP,
                 _offset_ptr(X, b0 * n * d), n * d, _offset_ptr(y, b0 * n), n, _offset_ptr(self.n_dev, b0),
                 _offset_ptr(self._W, b0 * lay.w_batch_stride), _offset_ptr(self._info, b0), _offset_ptr(out, b0 * 4),
-                _offset_ptr(mu, b0 * n), _offset_ptr(var, b0 * n), nat.ptr(g), nat.ptr(self._loo_work),
-                self._loo_work.numel() * 8, s), "gpk_loo_backward")
+                _offset_ptr(mu, b0 * n), _offset_ptr(var, b0 * n), nat.ptr(g), nat.ptr(work), work.numel() * 8, s),
+                "gpk_loo_backward")
             if gradient:
                 grads.extend(g[k] for k in range(b1 - b0))
         return out.view(B, 4)[:, 0], grads, mu, var
@@ -1175,47 +1148,19 @@ class RaggedInverseFactorization(AugmentedFactorization):
     # -- per-member read-out (device views, no host synchronisation) ---------------------------
     def gradients(self) -> torch.Tensor:
         """[B, n_hyp + 1] of a batch whose members share one program (the k-fold case)."""
-        if getattr(self, "_grads", None) is None or self.grad is None:
+        g = self._results["nlml"][1]
+        if g is None:
             raise RuntimeError("run(..., gradient=True) on members sharing one program first")
-        return self.grad
+        return g
 
     def gradient(self, b: int) -> torch.Tensor:
         """[n_hyp_b + 1] fp64: d(-LML_b)/d hyp (DFS order), then d(-LML_b)/d noise; NaN where info[b] != 0."""
-        if getattr(self, "_grads", None) is None:
+        if self._grads is None:
             raise RuntimeError("run(..., gradient=True) first")
-        for (b0, b1), g in zip(self._runs, self._grads):
+        for (b0, b1, _, _), g in zip(self._runs, self._grads):
             if b0 <= b < b1:
                 return g[b - b0]
         raise IndexError(b)
-
-    def corner(self, b: int = 0) -> torch.Tensor:
-        lay, nb = self.layout, self.sizes[b]
-        c = self.w(b)[lay.n_pad:lay.n_pad + nb, lay.n_pad:lay.n_pad + nb]
-        return torch.tril(c) + torch.tril(c, -1).transpose(0, 1)
-
-    def k_inv(self, b: int = 0) -> torch.Tensor:
-        """(K_b + noise I)^-1 [n_b, n_b], symmetrised from the corner's lower triangle."""
-        return -self.corner(b)
-
-    def extra_rows(self, b: int = 0) -> torch.Tensor:
-        lay, nb = self.layout, self.sizes[b]
-        return self.w(b)[lay.n_pad:lay.n_pad + nb, :nb]
-
-    def l_inv(self, b: int = 0) -> torch.Tensor:
-        """L_b^-1 (lower): the transpose of the extra rows, which hold L_b^-T."""
-        return torch.triu(self.extra_rows(b)).transpose(0, 1)
-
-    def cholesky(self, b: int = 0) -> torch.Tensor:
-        nb = self.sizes[b]
-        return torch.tril(self.w(b)[:nb, :nb])
-
-    def z(self, b: int = 0) -> torch.Tensor:
-        return self.w(b)[self.layout.y_row, :self.sizes[b]]
-
-    def alpha(self, b: int = 0) -> torch.Tensor:
-        """alpha_b [n_b], read from the corner's y row."""
-        lay = self.layout
-        return -self.w(b)[lay.y_row, lay.n_pad:lay.n_pad + self.sizes[b]].to(torch.float64)
 
     def alphas(self):
         return [self.alpha(b) for b in range(self.batch)]
@@ -1443,17 +1388,14 @@ class DenseFactorization(AugmentedFactorization):
         super().__init__(n, 1, n if inverse else m, batch, torch.float64)
 
     def run(self, A: torch.Tensor, noise, y: Optional[torch.Tensor] = None, E: Optional[torch.Tensor] = None):
-        self._pending = None
-        self._run_once(A, noise, y, E)
-        self._defer_verify(lambda: self._run_once(A, noise, y, E))
-        return self
+        return self._enqueue(self._run_once, A, noise, y, E)
 
     def _run_once(self, A, noise, y, E):
         A3, lda, abs_ = _mat_args(A, "A")
         B, n = self.batch, self.n
         if A3.shape[1] < n or A3.shape[2] < n or A3.shape[0] not in (1, B):
             raise ValueError("A must hold [%d, %d] per member" % (n, n))
-        dev = self.W.device
+        dev = self._dev
         noise_t = torch.as_tensor(noise, dtype=torch.float64).to(dev).reshape(-1).contiguous()
         if noise_t.numel() not in (1, B):
             raise ValueError("noise must be a scalar or one value per member")
@@ -1473,15 +1415,15 @@ class DenseFactorization(AugmentedFactorization):
         s = nat.stream_handle(dev)
         L = self.L
         lay = self.layout
-        self.info.zero_()
+        self._info.zero_()
         self._alphas = None
         nat.check(L.gpk_assemble_dense(ctypes.byref(lay), nat.ptr(A3), lda, abs_, nat.ptr(noise_t), ns,
                                        nat.ptr(E) if E is not None else None, ebs, int(self.inverse),
-                                       nat.ptr(y), ybs, nat.ptr(self.W), s), "gpk_assemble_dense")
-        nat.check(L.gpk_potrf_aug_ex(ctypes.byref(lay), nat.ptr(self.W), nat.ptr(self.Winv), nat.ptr(self.info),
+                                       nat.ptr(y), ybs, nat.ptr(self._W), s), "gpk_assemble_dense")
+        nat.check(L.gpk_potrf_aug_ex(ctypes.byref(lay), nat.ptr(self._W), nat.ptr(self._Winv), nat.ptr(self._info),
                                      nat.AUG_EXTRA_IDENTITY if self.inverse else 0, s), "gpk_potrf_aug_ex")
-        nat.check(L.gpk_finalize(ctypes.byref(lay), nat.ptr(self.W), nat.ptr(self.info), nat.ptr(self.out),
-                                 nat.ptr(self.mu) if self.m else None, nat.ptr(self.var) if self.m else None, s),
+        nat.check(L.gpk_finalize(ctypes.byref(lay), nat.ptr(self._W), nat.ptr(self._info), nat.ptr(self._out),
+                                 nat.ptr(self._mu) if self.m else None, nat.ptr(self._var) if self.m else None, s),
                   "gpk_finalize")
         self.done = True
         return self

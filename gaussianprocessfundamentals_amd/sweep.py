@@ -106,50 +106,73 @@ def native_batched_evaluator(kernel, X: torch.Tensor, y: torch.Tensor, noise, dt
     return evaluate
 
 
+def _check_candidates(cands: torch.Tensor, width: int, dev) -> None:
+    if cands.dim() != 2 or int(cands.shape[1]) != width:
+        raise ValueError("candidate rows must have %d values (hyperparameters, then the noise)" % width)
+    if cands.dtype != torch.float64 or cands.device != dev or not cands.is_contiguous():
+        raise ValueError("candidates must be a contiguous float64 tensor on %s" % (dev,))
+
+
+def _value_and_gradient(dev, width: int, make, run, kind: str = "nlml", n_folds: Optional[int] = None):
+    """The core of every native_*_value_and_gradient factory: f(cands [B, width] fp64 on ``dev``, the noise last,
+    settle=False) -> (f [B], g [B, width], info [B] int32) with ``.n_par`` (and ``.n_folds``).
+
+    ``make(B)`` builds what a batch of B candidates needs -- a factorisation of engine, or a tuple starting with one;
+    it is kept per B and reused.  ``run(state, hyp, hyp_stride, noise, noise_stride)`` enqueues one evaluation on it
+    and returns the factorisation, whose ``results(kind, settle)`` are the return value: unsettled views by default
+    (enqueue only, no host synchronisation), settled ones with ``settle=True`` (one 4-byte read-back, and only after
+    a persistent run; engine.AugmentedFactorization.results).  Candidate rows are read in place: the noise operand
+    is the same buffer from element width - 1 on (the last member's noise is its last element).  With ``n_folds``
+    = F the batch is S * F ragged members: the rows are replicated on the device (:func:`replicate_candidates`) and
+    the folds reduced in a fixed order (:func:`fold_mean`, :func:`fold_info`)."""
+    from . import _native as nat
+    cache = {}
+
+    def evaluate(cands: torch.Tensor, settle: bool = False):
+        _check_candidates(cands, width, dev)
+        B = int(cands.shape[0])
+        state = cache.get(B)
+        if state is None:
+            state = cache[B] = make(B)
+        if n_folds is None:
+            flat = cands.reshape(-1)
+            fac = run(state, flat, width, flat[width - 1:], width)
+            return fac.results(kind, settle)
+        hyp, noise = replicate_candidates(cands, n_folds, nat.MAX_HYP)
+        f, g, info = run(state, hyp, nat.MAX_HYP, noise, 1).results(kind, settle)
+        return fold_mean(f, n_folds), fold_mean(g, n_folds), fold_info(info, n_folds)
+
+    evaluate.n_par = width
+    if n_folds is not None:
+        evaluate.n_folds = n_folds
+    return evaluate
+
+
 def native_batched_value_and_gradient(kernel, X: torch.Tensor, y: torch.Tensor, dtype=None):
     """-LML and its gradient for a batch of (hyperparameters, noise) candidates by ONE identity-augmented batched
     factorisation per call (gpk_nlml_grad) -- the evaluation a multi-start fitter repeats (Optimizer.Fitter).
 
     Returns f(cands [B, n_hyp + 1] fp64 on the device, the noise last) -> (f [B], g [B, n_hyp + 1], info [B] int32):
-    device tensors, views of the factorisation's read-out and gradient buffers (valid until the next call with the
-    same B).  One engine.InverseFactorization per batch size is kept and reused; candidate rows are read in place
+    device tensors, views of the factorisation's read-out and gradient buffers (a new pair per call: earlier views
+    stay valid).  One engine.InverseFactorization per batch size is kept and reused; candidate rows are read in place
     (hyp_stride = noise_stride = n_hyp + 1).
 
     The call only enqueues: no host synchronisation.  A run that took the persistent launch is NOT settled by a plain
-    call (engine.CHAIN_VERIFY defers that to the first read through the factorisation's accessors, which these views
-    bypass): a wait that timed out shows as info = -1 for its members, which a fitter treats as a failed trial.
-    ``f(cands, settle=True)`` reads through the accessors instead: a persistent run is then verified (one 4-byte
-    read-back, which waits for it) and, had it timed out, run again on the launch path before the views are returned;
-    a run on the launch path has nothing to verify and does not synchronise.  A fitter settles the evaluations it is
-    about to synchronise on anyway, and the first one."""
+    call (engine.CHAIN_VERIFY defers that to the first settled read, which these views bypass): a wait that timed out
+    shows as info = -1 for its members, which a fitter treats as a failed trial.  ``f(cands, settle=True)`` reads the
+    settled results instead: a persistent run is then verified (one 4-byte read-back, which waits for it) and, had it
+    timed out, run again on the launch path before the views are returned; a run on the launch path has nothing to
+    verify and does not synchronise.  A fitter settles the evaluations it is about to synchronise on anyway, and the
+    first one."""
     X = engine.as_device_f64(X)
     yv = engine.as_device_f64(y).reshape(1, -1).contiguous()
     n, d = int(X.shape[0]), int(X.shape[1])
     if int(yv.shape[1]) != n:
         raise ValueError("y has %d values, X has %d points" % (int(yv.shape[1]), n))
     kd = engine.kernel_descriptor(kernel, d)
-    width = kd.n_hyp + 1
     dt = dtype or gp.p_dtype
-    cache = {}
-
-    def evaluate(cands: torch.Tensor, settle: bool = False):
-        if cands.dim() != 2 or int(cands.shape[1]) != width:
-            raise ValueError("candidate rows must have %d values (hyperparameters, then the noise)" % width)
-        if cands.dtype != torch.float64 or cands.device != X.device or not cands.is_contiguous():
-            raise ValueError("candidates must be a contiguous float64 tensor on %s" % (X.device,))
-        B = int(cands.shape[0])
-        f = cache.get(B)
-        if f is None:
-            f = cache[B] = engine.InverseFactorization(n, d, B, dt)
-        flat = cands.reshape(-1)
-        # (the noise operand: the same buffer from element n_hyp on; the last member's noise is its last element)
-        f.run(kd, flat, width, flat[kd.n_hyp:], width, X, 0, yv, 0, gradient=True)
-        if settle:
-            return f.nlml(), f.gradient(), f.info
-        return f._out.view(B, 4)[:, 0], f.grad, f._info
-
-    evaluate.n_par = width
-    return evaluate
+    return _value_and_gradient(X.device, kd.n_hyp + 1, lambda B: engine.InverseFactorization(n, d, B, dt),
+                               lambda f, h, hs, nz, ns: f.run(kd, h, hs, nz, ns, X, 0, yv, 0, gradient=True))
 
 
 def replicate_candidates(cands: torch.Tensor, n_folds: int, width: int):
@@ -177,6 +200,24 @@ def fold_info(info: torch.Tensor, n_folds: int) -> torch.Tensor:
     return info.reshape(-1, n_folds).abs().amax(dim=1).to(torch.int32)
 
 
+def _pack_folds(folds, with_test: bool):
+    """Folds of device tensors (X_f [n_f, d], y_f [n_f][, Xs_f [m_f, d], ys_f [m_f]]) -> [Xf [F, n, d], yf [F, n]
+    (, Xsf [F, m, d], ysf [F, m])] with n / m the largest fold's counts, zero-filled past each fold's own."""
+    def pad(parts):
+        out = torch.zeros((len(parts), max(int(t.shape[0]) for t in parts)) + tuple(parts[0].shape[1:]),
+                          dtype=torch.float64, device=parts[0].device)
+        for k, t in enumerate(parts):
+            out[k, :int(t.shape[0])] = t
+        return out
+    columns = list(zip(*folds))   # (every fold's X, every fold's y[, every fold's Xs, every fold's ys])
+    return [pad(parts) for parts in columns[:4 if with_test else 2]]
+
+
+def _replicate(packed, S: int):
+    """The packed fold operands [F, ...] tiled to the S * F members of S candidates (member s * F + f: fold f)."""
+    return [t.repeat((S,) + (1,) * (t.dim() - 1)).contiguous() for t in packed]
+
+
 def native_kfold_value_and_gradient(kernel, folds, dtype=None):
     """Mean over k folds of -LML and of its gradient for a batch of (hyperparameters, noise) candidates: the reference's
     opt_kfold / opt_optimize_noise_kfold objective (gpbasics/Optimizer/Fitter.py:97-102) under its tape, as ONE ragged
@@ -190,7 +231,6 @@ def native_kfold_value_and_gradient(kernel, folds, dtype=None):
     and the folds reduced in a fixed order (:func:`fold_mean`).  The call only enqueues: no host synchronisation
     (``settle`` is accepted for the signature of native_batched_value_and_gradient: ragged batches never take the
     persistent launch, so there is nothing to verify)."""
-    from . import _native as nat
     folds = [(engine.as_device_f64(X), engine.as_device_f64(y).reshape(-1)) for X, y in folds]
     if not folds:
         raise ValueError("at least one fold is needed")
@@ -201,44 +241,19 @@ def native_kfold_value_and_gradient(kernel, folds, dtype=None):
         if X.dim() != 2 or int(X.shape[1]) != d or int(y.numel()) != int(X.shape[0]) or int(X.shape[0]) < 1:
             raise ValueError("every fold needs X [n_f >= 1, %d] and y with n_f values" % d)
         sizes.append(int(X.shape[0]))
-    n = max(sizes)
-    dev = folds[0][0].device
     kd = engine.kernel_descriptor(kernel, d)
-    width = kd.n_hyp + 1
     dt = dtype or gp.p_dtype
-    Xf = torch.zeros((F, n, d), dtype=torch.float64, device=dev)
-    yf = torch.zeros((F, n), dtype=torch.float64, device=dev)
-    for k, (X, y) in enumerate(folds):
-        Xf[k, :sizes[k]] = X
-        yf[k, :sizes[k]] = y
-    cache = {}
+    packed = _pack_folds(folds, False)
 
-    def evaluate(cands: torch.Tensor, settle: bool = False):
-        if cands.dim() != 2 or int(cands.shape[1]) != width:
-            raise ValueError("candidate rows must have %d values (hyperparameters, then the noise)" % width)
-        if cands.dtype != torch.float64 or cands.device != dev or not cands.is_contiguous():
-            raise ValueError("candidates must be a contiguous float64 tensor on %s" % (dev,))
-        S = int(cands.shape[0])
-        slot = cache.get(S)
-        if slot is None:
-            fac = engine.RaggedInverseFactorization(sizes * S, d, dt)
-            slot = cache[S] = (fac, Xf.repeat(S, 1, 1).contiguous(), yf.repeat(S, 1).contiguous(), [kd] * (S * F))
-        fac, Xp, yp, kds = slot
-        hyp, noise = replicate_candidates(cands, F, nat.MAX_HYP)
-        fac.run_packed(kds, hyp, noise, Xp, yp, gradient=True)
-        return (fold_mean(fac._out.view(S * F, 4)[:, 0], F), fold_mean(fac.gradients(), F),
-                fold_info(fac._info, F))
+    def make(S):
+        Xp, yp = _replicate(packed, S)
+        return engine.RaggedInverseFactorization(sizes * S, d, dt), [kd] * (S * F), Xp, yp
 
-    evaluate.n_par = width
-    evaluate.n_folds = F
-    return evaluate
+    def run(state, hyp, hyp_stride, noise, noise_stride):   # (packed operands: the strides are the layout's own)
+        fac, kds, Xp, yp = state
+        return fac.run_packed(kds, hyp, noise, Xp, yp, gradient=True)
 
-
-def _check_candidates(cands: torch.Tensor, width: int, dev) -> None:
-    if cands.dim() != 2 or int(cands.shape[1]) != width:
-        raise ValueError("candidate rows must have %d values (hyperparameters, then the noise)" % width)
-    if cands.dtype != torch.float64 or cands.device != dev or not cands.is_contiguous():
-        raise ValueError("candidates must be a contiguous float64 tensor on %s" % (dev,))
+    return _value_and_gradient(folds[0][0].device, kd.n_hyp + 1, make, run, n_folds=F)
 
 
 def _check_mse_shapes(X, y, Xs, ys, d=None):
@@ -257,6 +272,10 @@ def _check_mse_shapes(X, y, Xs, ys, d=None):
     return n, m, dd
 
 
+def _as_tensor(t) -> torch.Tensor:
+    return t if isinstance(t, torch.Tensor) else torch.as_tensor(t)
+
+
 def native_batched_mse_value_and_gradient(kernel, X: torch.Tensor, y: torch.Tensor, Xs: torch.Tensor,
                                           ys: torch.Tensor):
     """Held-out MSE mean((K_s^T (K + noise I)^-1 y - y_test)^2) and its gradient for a batch of (hyperparameters,
@@ -265,32 +284,17 @@ def native_batched_mse_value_and_gradient(kernel, X: torch.Tensor, y: torch.Tens
 
     Returns f(cands [B, n_hyp + 1] fp64 on the device, the noise last, settle=False) -> (f [B], g [B, n_hyp + 1],
     info [B] int32): the contract of :func:`native_batched_value_and_gradient` -- ``.n_par``, candidate rows read in
-    place, enqueue only, ``settle=True`` reads through the factorisation's accessors (a persistent run is then
-    verified and, had it timed out, run again on the launch path).  fp64 only."""
-    as_t = lambda t: t if isinstance(t, torch.Tensor) else torch.as_tensor(t)
-    n, m, d = _check_mse_shapes(as_t(X), as_t(y), as_t(Xs), as_t(ys))
+    place, enqueue only, ``settle=True`` reads the settled results (a persistent run is then verified and, had it
+    timed out, run again on the launch path).  fp64 only."""
+    n, m, d = _check_mse_shapes(_as_tensor(X), _as_tensor(y), _as_tensor(Xs), _as_tensor(ys))
     X, Xs = engine.as_device_f64(X).contiguous(), engine.as_device_f64(Xs).contiguous()
     yv = engine.as_device_f64(y).reshape(1, -1).contiguous()
     ysv = engine.as_device_f64(ys).reshape(1, -1).contiguous()
     kd = engine.kernel_descriptor(kernel, d)
-    width = kd.n_hyp + 1
-    cache = {}
-
-    def evaluate(cands: torch.Tensor, settle: bool = False):
-        _check_candidates(cands, width, X.device)
-        B = int(cands.shape[0])
-        f = cache.get(B)
-        if f is None:
-            f = cache[B] = engine.AugmentedFactorization(n, d, m, B, torch.float64)
-        flat = cands.reshape(-1)
-        # (the noise operand: the same buffer from element n_hyp on; the last member's noise is its last element)
-        f.run_mse(kd, flat, width, flat[kd.n_hyp:], width, X, 0, yv, 0, Xs, 0, ysv, 0)
-        if settle:
-            return f.mse(), f.mse_grad(), f.info
-        return f.unsettled_mse()
-
-    evaluate.n_par = width
-    return evaluate
+    return _value_and_gradient(X.device, kd.n_hyp + 1,
+                               lambda B: engine.AugmentedFactorization(n, d, m, B, torch.float64),
+                               lambda f, h, hs, nz, ns: f.run_mse(kd, h, hs, nz, ns, X, 0, yv, 0, Xs, 0, ysv, 0),
+                               kind="mse")
 
 
 def native_batched_loo_value_and_gradient(kernel, X: torch.Tensor, y: torch.Tensor, loss, dtype=None):
@@ -301,40 +305,24 @@ def native_batched_loo_value_and_gradient(kernel, X: torch.Tensor, y: torch.Tens
 
     Returns f(cands [B, n_hyp + 1] fp64 on the device, the noise last, settle=False) -> (f [B], g [B, n_hyp + 1],
     info [B] int32): the contract of :func:`native_batched_value_and_gradient` -- ``.n_par``, candidate rows read in
-    place, enqueue only, ``settle=True`` reads through the factorisation's accessors (a persistent run is then
-    verified and, had it timed out, run again on the launch path).  fp64 only (``dtype``: None or torch.float64)."""
+    place, enqueue only, ``settle=True`` reads the settled results (a persistent run is then verified and, had it
+    timed out, run again on the launch path).  fp64 only (``dtype``: None or torch.float64)."""
     from . import _native as nat
     if dtype not in (None, torch.float64):
         raise NotImplementedError("leave-one-out is fp64 only")
     code = nat.loo_loss_code(loss)
-    as_t = lambda t: t if isinstance(t, torch.Tensor) else torch.as_tensor(t)
-    if as_t(X).dim() != 2 or int(as_t(X).shape[0]) < 1:
+    if _as_tensor(X).dim() != 2 or int(_as_tensor(X).shape[0]) < 1:
         raise ValueError("X must be [n >= 1, d]")
-    n, d = int(as_t(X).shape[0]), int(as_t(X).shape[1])
-    if int(as_t(y).numel()) != n:
-        raise ValueError("y has %d values, X has %d points" % (int(as_t(y).numel()), n))
+    n, d = int(_as_tensor(X).shape[0]), int(_as_tensor(X).shape[1])
+    if int(_as_tensor(y).numel()) != n:
+        raise ValueError("y has %d values, X has %d points" % (int(_as_tensor(y).numel()), n))
     X = engine.as_device_f64(X).contiguous()
     yv = engine.as_device_f64(y).reshape(1, -1).contiguous()
     kd = engine.kernel_descriptor(kernel, d)
-    width = kd.n_hyp + 1
-    cache = {}
-
-    def evaluate(cands: torch.Tensor, settle: bool = False):
-        _check_candidates(cands, width, X.device)
-        B = int(cands.shape[0])
-        f = cache.get(B)
-        if f is None:
-            f = cache[B] = engine.InverseFactorization(n, d, B, torch.float64)
-        flat = cands.reshape(-1)
-        # (the noise operand: the same buffer from element n_hyp on; the last member's noise is its last element)
-        f.run_loo(code, kd, flat, width, flat[kd.n_hyp:], width, X, 0, yv, 0, gradient=True)
-        if settle:
-            v, g, _, _ = f.loo_results()
-            return v, g, f.info
-        return f.unsettled_loo()
-
-    evaluate.n_par = width
-    return evaluate
+    return _value_and_gradient(X.device, kd.n_hyp + 1,
+                               lambda B: engine.InverseFactorization(n, d, B, torch.float64),
+                               lambda f, h, hs, nz, ns: f.run_loo(code, kd, h, hs, nz, ns, X, 0, yv, 0, gradient=True),
+                               kind="loo")
 
 
 def native_kfold_mse_value_and_gradient(kernel, folds):
@@ -348,52 +336,29 @@ def native_kfold_mse_value_and_gradient(kernel, folds):
     contributes its own MSE, the folds are reduced in a fixed order (:func:`fold_mean`, :func:`fold_info`); f is +inf
     and g NaN where any fold's factorisation failed.  Enqueue only (ragged batches never take the persistent launch:
     ``settle`` has nothing to verify)."""
-    from . import _native as nat
     if not folds:
         raise ValueError("at least one fold is needed")
-    as_t = lambda t: t if isinstance(t, torch.Tensor) else torch.as_tensor(t)
     d, sizes, tsizes = None, [], []
     for fold in folds:
         if len(fold) != 4:
             raise ValueError("every fold is (X, y, X_test, y_test)")
-        nf, mf, d = _check_mse_shapes(*[as_t(t) for t in fold], d=d)
+        nf, mf, d = _check_mse_shapes(*[_as_tensor(t) for t in fold], d=d)
         sizes.append(nf)
         tsizes.append(mf)
     folds = [(engine.as_device_f64(X), engine.as_device_f64(y).reshape(-1), engine.as_device_f64(Xs),
               engine.as_device_f64(ys).reshape(-1)) for X, y, Xs, ys in folds]
-    F = len(folds)
-    n, m = max(sizes), max(tsizes)
-    dev = folds[0][0].device
     kd = engine.kernel_descriptor(kernel, d)
-    width = kd.n_hyp + 1
-    Xf = torch.zeros((F, n, d), dtype=torch.float64, device=dev)
-    yf = torch.zeros((F, n), dtype=torch.float64, device=dev)
-    Xsf = torch.zeros((F, m, d), dtype=torch.float64, device=dev)
-    ysf = torch.zeros((F, m), dtype=torch.float64, device=dev)
-    for k, (X, y, Xs, ys) in enumerate(folds):
-        Xf[k, :sizes[k]] = X
-        yf[k, :sizes[k]] = y
-        Xsf[k, :tsizes[k]] = Xs
-        ysf[k, :tsizes[k]] = ys
-    cache = {}
+    packed = _pack_folds(folds, True)
 
-    def evaluate(cands: torch.Tensor, settle: bool = False):
-        _check_candidates(cands, width, dev)
-        S = int(cands.shape[0])
-        slot = cache.get(S)
-        if slot is None:
-            fac = engine.RaggedFactorization(sizes * S, d, tsizes * S, torch.float64)
-            slot = cache[S] = (fac, Xf.repeat(S, 1, 1).contiguous(), yf.repeat(S, 1).contiguous(),
-                               Xsf.repeat(S, 1, 1).contiguous(), ysf.repeat(S, 1).contiguous())
-        fac, Xp, yp, Xsp, ysp = slot
-        hyp, noise = replicate_candidates(cands, F, nat.MAX_HYP)
-        fac.run_mse_packed(kd, hyp, noise, Xp, yp, Xsp, ysp)
-        mse, grad, info = fac.unsettled_mse()
-        return fold_mean(mse, F), fold_mean(grad, F), fold_info(info, F)
+    def make(S):
+        Xp, yp, Xsp, ysp = _replicate(packed, S)
+        return engine.RaggedFactorization(sizes * S, d, tsizes * S, torch.float64), Xp, yp, Xsp, ysp
 
-    evaluate.n_par = width
-    evaluate.n_folds = F
-    return evaluate
+    def run(state, hyp, hyp_stride, noise, noise_stride):   # (packed operands: the strides are the layout's own)
+        fac, Xp, yp, Xsp, ysp = state
+        return fac.run_mse_packed(kd, hyp, noise, Xp, yp, Xsp, ysp)
+
+    return _value_and_gradient(folds[0][0].device, kd.n_hyp + 1, make, run, kind="mse", n_folds=len(folds))
 
 
 class HyperparameterSweep:

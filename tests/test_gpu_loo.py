@@ -141,7 +141,8 @@ def test_determinism_and_w_intact(loss):
     b = [t.clone() for t in fac.loo(loss)]
     for u, v in zip(a, b):
         assert torch.equal(u, v)
-    assert torch.equal(fac.W, w) and torch.equal(fac.nlml(), nl)
+    # (bit patterns: W's never-written padding is the allocator's, and may hold NaN, which torch.equal calls unequal)
+    assert torch.equal(fac.W.view(torch.int64), w.view(torch.int64)) and torch.equal(fac.nlml(), nl)
     for k in range(3):
         assert torch.equal(fac.k_inv(k), before[k][0]) and torch.equal(fac.alpha(k), before[k][1])
     # the composite (gpk_loo_grad) on a fresh object: the pass's bits

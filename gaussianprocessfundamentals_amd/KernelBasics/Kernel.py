@@ -27,6 +27,25 @@ def _abstract(obj, name):
     return NotImplementedError("%s.%s is provided by the concrete kernel" % (type(obj).__name__, name))
 
 
+def split_derivative_planes(planes: torch.Tensor, hyper_parameter: List) -> List[torch.Tensor]:
+    """Flat planes [n_hyp, n, m] (DFS order) -> the list aligned with ``hyper_parameter``: entry k is a view of shape
+    ``hyper_parameter[k].shape + (n, m)``."""
+    shapes = [tuple(torch.as_tensor(h).shape) for h in hyper_parameter]
+    counts = [max(1, int(torch.Size(s).numel())) for s in shapes]
+    if planes.dim() != 3 or planes.shape[0] != sum(counts):
+        raise ValueError("expected %d derivative planes [n_hyp, n, m], got %s" % (sum(counts), tuple(planes.shape)))
+    out, i = [], 0
+    for s, k in zip(shapes, counts):
+        out.append(planes[i:i + k].reshape(s + tuple(planes.shape[1:])))
+        i += k
+    return out
+
+
+def stack_derivative_planes(matrices: List[torch.Tensor]) -> torch.Tensor:
+    """The inverse of split_derivative_planes: the list's entries [..., n, m] as flat planes [n_hyp, n, m]."""
+    return torch.cat([m.reshape((-1,) + tuple(m.shape[-2:])) for m in matrices], dim=0)
+
+
 class Kernel(bgpc.Component):
     """Abstract kernel: a node of a kernel expression tree."""
 
@@ -107,12 +126,26 @@ class Kernel(bgpc.Component):
         raise _abstract(self, 'get_number_of_child_nodes')
 
     def get_derivative_matrices(self, hyper_parameter: List, x_vector, x_vector_) -> List:
-        # not rebuilt: nothing in the reference calls them (its fitter differentiates through
-        # tf.linalg.cholesky), SE's is wrong (K/BaseKernels.py:383-399), and the LML gradient is computed by
-        # the fused device pass of gpk_nlml_grad without any dK/dtheta matrix (LogLikelihood.get_metric_and_gradient).
-        # LinearKernel's (get_c_derivative_matrix, K/BaseKernels.py:232-241) is not rebuilt either.
-        raise NotImplementedError("analytic derivative matrices are not provided: use "
-                                  "LogLikelihood.get_metric_and_gradient or autograd through get_metric")
+        """The derivative matrices d K(x_vector, x_vector_) / d hyper_parameter, a list aligned with
+        ``hyper_parameter``: entry k has the shape ``hyper_parameter[k].shape + (n, m)`` -- [n, m] for a scalar,
+        [d, n, m] for an ARD vector -- as fp64 device tensors (views of one gpk_kernel_jacobian result).  Base kernels
+        and operators alike; ChangePointOperator in its 1-D device form.
+
+        These are the true derivatives of the kernel as this library evaluates it, with respect to the values as
+        passed: sign(l) for the Matern kernels' |l|, the analytic 0 of the distance terms at coincident points, 0 for
+        the hard change-point mask.  They are deliberately NOT the reference's dead ``get_*_derivative_matrix``
+        forms (K/BaseKernels.py:383-399, :232-241), of which SE's and LIN's are not derivatives of their kernels
+        (DESIGN.md §7).  Records ``last_hyper_parameter`` as get_tf_tensor does."""
+        assert x_vector is not None and x_vector_ is not None, "Input vectors x and x_ uninitialized: " + str(self)
+        assert len(hyper_parameter) == self.get_number_of_hyper_parameter(), "Invalid hyper_param size: " + str(self)
+        planes = self._derivative_planes(hyper_parameter, x_vector, x_vector_)
+        self._record_hyper_parameter(list(hyper_parameter))
+        return split_derivative_planes(planes, hyper_parameter)
+
+    def _derivative_planes(self, hyper_parameter: List, x_vector, x_vector_) -> torch.Tensor:
+        """[n_hyp, n, m]: one plane per flat hyperparameter in DFS order (engine.kernel_jacobian)."""
+        from .. import engine
+        return engine.kernel_jacobian(self, hyper_parameter, x_vector, x_vector_)
 
     def get_hyper_parameter_names(self, kernel_id: int = -1) -> List[str]:
         raise _abstract(self, 'get_hyper_parameter_names')

@@ -262,6 +262,23 @@ class LogLikelihood(AbstractLogLikelihood):
         _, grads, _ = self.get_metric_and_gradient(hyper_parameter, noise, reset=reset)
         return torch.cat([g.reshape(-1) for g in grads]) if grads else torch.zeros(0, dtype=torch.float64)
 
+    def get_fisher_information(self, hyper_parameter: List, noise) -> torch.Tensor:
+        """The Fisher information of the kernel hyperparameters and the noise, F_pq = 1/2 tr(K^-1 d_pK K^-1 d_qK)
+        with d_noise K = I: a [P + 1, P + 1] fp64 device tensor, the hyperparameters flattened in DFS order, the noise
+        last (engine.InverseFactorization.fisher -> gpk_fisher, on the factorisation the gradient runs).  It is the
+        expected Hessian of -LML; it does not depend on y, so any mean function is fine.  NaN when K + noise I is not
+        positive definite.  DataInput, exact, CHOLESKY_BASED."""
+        name = "LogLikelihood.get_fisher_information"
+        if self.data_input.data_x_train.dim() == 3:
+            raise NotImplementedError("%s: BatchDataInput is not supported" % name)
+        if self.local_approx is not mht.MatrixApproximations.NONE:
+            raise NotImplementedError("%s: approximation %s is not supported" % (name, self.local_approx.name))
+        if self.numerical_matrix_handling is not mht.NumericalMatrixHandlingType.CHOLESKY_BASED:
+            raise NotImplementedError("%s: matrix handling %s is not supported (CHOLESKY_BASED)"
+                                      % (name, self.numerical_matrix_handling.name))
+        f = self.covariance_matrix.inverse_factorization(hyper_parameter, noise, gradient=False)
+        return f.fisher()[0]
+
     def get_metric_checked(self, hyper_parameter: List, noise, reset: bool = True) -> torch.Tensor:
         """get_metric that raises CholeskyError when K + noise I is not positive definite
         (the reference's TensorFlow raises from tf.linalg.cholesky); synchronises."""

@@ -266,6 +266,61 @@ class DeviceLbfgsFitter(GradientFitter):
         # (get_metric records its argument in the kernel, SURVEY Q9: the same list)
         return pre_fit_metric, post_fit_metric, kernel.get_last_hyper_parameter(), kernel.get_noise(), None
 
+    # -- after the fit: how well the data determine the point -----------------------------------------
+    _FISHER_OBJECTIVE = True   # the objective is -LML of one DataInput: its Fisher information is the fit's curvature
+
+    def _require_fisher_objective(self, what: str) -> None:
+        if not self._FISHER_OBJECTIVE:
+            raise NotImplementedError("%s.%s: the objective of this fitter is not -LML of one data input, so the Fisher "
+                                      "information of the likelihood is not the curvature of what was fitted"
+                                      % (type(self).__name__, what))
+        if getattr(self, "points", None) is None:
+            raise RuntimeError("%s.%s: fit() first" % (type(self).__name__, what))
+
+    def fisher_information(self) -> torch.Tensor:
+        """F [n_hyp + 1, n_hyp + 1] (device) at the winning point of the last ``fit``: hyperparameters in DFS order,
+        the noise last, from one B = 1 identity-augmented factorisation (engine.InverseFactorization.fisher)."""
+        self._require_fisher_objective("fisher_information")
+        from .. import engine
+        di = self.data_input
+        x = engine.as_device_f64(di.data_x_train).contiguous()
+        n, d = int(x.shape[0]), int(x.shape[1])
+        y = engine.as_device_f64(di.get_detrended_y_train()).reshape(1, n).contiguous()
+        kd = engine.kernel_descriptor(self._kernel(), d)
+        point = engine.host_f64_to_device([float(v) for v in self.points[self.winner]])
+        f = engine.InverseFactorization(n, d, 1, torch.float64)
+        f.run(kd, point[:-1], 0, point[-1:], 0, x, 0, y, 0, gradient=False)
+        return f.fisher()[0]
+
+    def standard_errors(self) -> torch.Tensor:
+        """[n_hyp + 1] host tensor: sqrt(diag(F_free^-1)) of the winning point, scattered back to every position
+        (:func:`standard_errors_from_fisher`).  NaN for a parameter that is pinned (lo == hi, e.g. the noise when
+        p_optimize_noise is off) or sits on a bound; inf for a free parameter the data say nothing about."""
+        self._require_fisher_objective("standard_errors")
+        lo, hi = self.bounds()
+        point = [float(v) for v in self.points[self.winner]]
+        free = [lo[i] < point[i] < hi[i] for i in range(len(point))]
+        return standard_errors_from_fisher(self.fisher_information().cpu(), free)
+
+
+def standard_errors_from_fisher(fisher, free) -> torch.Tensor:
+    """sqrt(diag(F_free^-1)) scattered to all positions (host, fp64): NaN where ``free`` is false, inf for a free
+    parameter whose row of F is zero (no information), the inverse taken over the remaining ones."""
+    import numpy as np
+    F = np.asarray(torch.as_tensor(fisher, dtype=torch.float64).cpu())
+    out = np.full(F.shape[0], np.nan)
+    idx = [i for i in range(F.shape[0]) if free[i]]
+    blind = [i for i in idx if not np.any(F[i, idx] != 0.0)]
+    out[blind] = np.inf
+    rest = [i for i in idx if i not in blind]
+    if rest:
+        try:
+            var = np.diag(np.linalg.inv(F[np.ix_(rest, rest)]))
+            out[rest] = np.where(var >= 0.0, np.sqrt(np.abs(var)), np.nan)
+        except np.linalg.LinAlgError:   # (exactly singular among parameters that each have information)
+            out[rest] = np.inf
+    return torch.from_numpy(out)
+
 
 class DeviceKfoldLbfgsFitter(DeviceLbfgsFitter):
     """:class:`DeviceLbfgsFitter` for a k-fold list of DataInputs: the objective is the mean of the folds' -LML
@@ -274,6 +329,8 @@ class DeviceKfoldLbfgsFitter(DeviceLbfgsFitter):
     of Metrics/CrossValidation.get_data_inputs differ in n_train whenever n is not divisible.  The constructor arguments
     are the sibling's; ``data_input`` is the list.  xrange and n of the defaults and bounds come from fold 0, as
     upstream (Fitter.py:64-66); the pre- and post-fit metrics are the mean of the folds' ``get_metric``."""
+
+    _FISHER_OBJECTIVE = False
 
     @classmethod
     def _check_data_input(cls, data_input):
@@ -316,6 +373,8 @@ class DeviceMseLbfgsFitter(DeviceLbfgsFitter):
     test points as extra rows plus the MSE gradient pass (sweep.native_batched_mse_value_and_gradient ->
     gpk_mse_grad).  Pre- and post-fit metrics are MeanSquaredError.get_metric.  With a scaled kernel and an optimised
     noise the MSE is invariant along (sg, noise) -> (c sg, c noise): the minimiser is a ray, compare objective values."""
+
+    _FISHER_OBJECTIVE = False
 
     _METRICS = (met.MetricType.MSE,)
 
@@ -361,6 +420,8 @@ class DeviceLooLbfgsFitter(DeviceLbfgsFitter):
     factorisation plus the LOO pass (sweep.native_batched_loo_value_and_gradient -> gpk_loo_grad).  Pre- and post-fit
     metrics are LeaveOneOut.get_metric.  The LOO-MSE is invariant under K -> c K: with a scaled kernel and an optimised
     noise its minimiser is a ray, compare objective values (or pin the noise)."""
+
+    _FISHER_OBJECTIVE = False
 
     _METRICS = (met.MetricType.LL, met.MetricType.MSE)
 

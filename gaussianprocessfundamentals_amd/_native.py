@@ -45,6 +45,7 @@ EXPORTS = (
     "gpk_assemble_inverse_ragged", "gpk_potrf_aug_ragged_ex", "gpk_grad_ragged", "gpk_nlml_grad_ragged",
     "gpk_launch_plan", "gpk_mse_grad_workspace_bytes", "gpk_mse_backward", "gpk_mse_grad",
     "gpk_loo_workspace_bytes", "gpk_loo_backward", "gpk_loo_grad",
+    "gpk_kernel_jacobian_workspace_bytes", "gpk_kernel_jacobian", "gpk_fisher_workspace_bytes", "gpk_fisher",
 )
 # the ragged identity-augmented entries (added without a new ABI number, found by symbol)
 RAGGED_GRAD_ENTRIES = ("gpk_assemble_inverse_ragged", "gpk_potrf_aug_ragged_ex", "gpk_grad_ragged",
@@ -54,6 +55,9 @@ MSE_GRAD_ENTRIES = ("gpk_mse_grad_workspace_bytes", "gpk_mse_backward", "gpk_mse
 # leave-one-out cross-validation (likewise); the losses of include/gpk.h
 LOO_ENTRIES = ("gpk_loo_workspace_bytes", "gpk_loo_backward", "gpk_loo_grad")
 LOO_LPD, LOO_MSE = 0, 1
+# the kernel derivative matrices and the Fisher information (likewise)
+FISHER_ENTRIES = ("gpk_kernel_jacobian_workspace_bytes", "gpk_kernel_jacobian", "gpk_fisher_workspace_bytes",
+                  "gpk_fisher")
 
 
 class NativeUnavailable(RuntimeError):
@@ -197,10 +201,16 @@ def _declare(lib):
                                      c_int64, P, P, P, P, P, P, P, P, c_size_t, P]),
         "gpk_loo_grad": (c_int, [c_int32, POINTER(GpkKdesc), POINTER(GpkLayout), P, c_int64, P, c_int64, P, c_int64, P,
                                  c_int64, P, P, P, P, P, P, P, P, P, c_size_t, P]),
+        "gpk_kernel_jacobian_workspace_bytes": (c_size_t, [POINTER(GpkKdesc), c_int64, c_int64, c_int32]),
+        "gpk_kernel_jacobian": (c_int, [POINTER(GpkKdesc), P, c_int64, c_int32, P, c_int64, c_int64, P, c_int64,
+                                        c_int64, c_int32, P, c_int64, c_int64, c_int64, P, c_size_t, P]),
+        "gpk_fisher_workspace_bytes": (c_size_t, [POINTER(GpkKdesc), POINTER(GpkLayout)]),
+        "gpk_fisher": (c_int, [POINTER(GpkKdesc), POINTER(GpkLayout), P, c_int64, P, c_int64, P, P, P, P, c_size_t,
+                               P]),
     }
     for name, (res, args) in sig.items():
         if (name in ("gpk_op_supported", "gpk_launch_plan") or name in RAGGED_GRAD_ENTRIES or
-                name in MSE_GRAD_ENTRIES or name in LOO_ENTRIES or
+                name in MSE_GRAD_ENTRIES or name in LOO_ENTRIES or name in FISHER_ENTRIES or
                 name.startswith(("gpk_mean_", "gpk_fit_"))) and not hasattr(lib, name):
             continue  # (a library built before the entry existed: *op_supported() / fit_supported() then say no)
         fn = getattr(lib, name)
@@ -287,6 +297,20 @@ def require_loo(library=None):
     if not loo_supported(library):
         raise NativeUnavailable("this libgpk.so was built before the leave-one-out entries (gpk_loo_grad and its kin) "
                                 "existed: rebuild it")
+
+
+def fisher_supported(library=None) -> bool:
+    """Whether the library has the derivative-matrix and Fisher entries (gpk_kernel_jacobian, gpk_fisher and their
+    workspace queries; added without a new ABI number); False for one built before they existed -- it still loads, and
+    the engine's kernel_jacobian / fisher calls raise NativeUnavailable."""
+    L = library if library is not None else load_library()
+    return all(hasattr(L, n) for n in FISHER_ENTRIES)
+
+
+def require_fisher(library=None):
+    if not fisher_supported(library):
+        raise NativeUnavailable("this libgpk.so was built before the derivative-matrix and Fisher entries "
+                                "(gpk_kernel_jacobian, gpk_fisher) existed: rebuild it")
 
 
 def loo_loss_code(loss) -> int:

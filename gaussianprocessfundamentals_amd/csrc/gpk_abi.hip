@@ -1869,6 +1869,93 @@ int gpk_kernel_vjp(const gpk_kdesc* kd, const double* hyp_dev, const double* X, 
   return 0;
 }
 
+size_t gpk_kernel_jacobian_workspace_bytes(const gpk_kdesc* kd, int64_t n, int64_t m, int32_t d) {
+  (void)kd, (void)n, (void)m, (void)d;
+  return 0;  // the planes are written directly: no partial sums
+}
+
+int gpk_kernel_jacobian(const gpk_kdesc* kd, const double* hyp_dev, int64_t hyp_stride, int32_t batch, const double* X,
+                        int64_t n, int64_t x_bstride, const double* Z, int64_t m, int64_t z_bstride, int32_t d,
+                        double* J, int64_t ldj, int64_t plane_stride, int64_t j_bstride, void* work, size_t work_bytes,
+                        void* stream) {
+  (void)work, (void)work_bytes;
+  if (!valid_kdesc(kd, d)) return fail_arg(1, "kernel descriptor");
+  if (!hyp_dev && kd->n_hyp > 0) return fail_arg(2, "hyp_dev");
+  if (batch <= 0 || batch > 65535) return fail_arg(4, "batch (1 .. 65535)");
+  if (batch > 1 && hyp_stride != 0 && hyp_stride < kd->n_hyp) return fail_arg(3, "hyp_stride");
+  if (!X) return fail_arg(5, "X");
+  if (n <= 0) return fail_arg(6, "n");
+  if (batch > 1 && x_bstride != 0 && x_bstride < n * d) return fail_arg(7, "x_bstride");
+  if (!Z) return fail_arg(8, "Z");
+  if (m <= 0) return fail_arg(9, "m");
+  if (batch > 1 && z_bstride != 0 && z_bstride < m * d) return fail_arg(10, "z_bstride");
+  if (d <= 0 || d > GPK_MAX_DIM) return fail_arg(11, "d");
+  if (kd->n_hyp == 0) return 0;  // no plane to write
+  if (!J) return fail_arg(12, "J");
+  if (ldj < m) return fail_arg(13, "ldj");
+  if (kd->n_hyp > 1 && plane_stride < (n - 1) * ldj + m) return fail_arg(14, "plane_stride");
+  if (batch > 1 && j_bstride < (kd->n_hyp - 1) * plane_stride + (n - 1) * ldj + m) return fail_arg(15, "j_bstride");
+  JacArgs g;
+  memset(&g, 0, sizeof(g));
+  g.hyp = hyp_dev;
+  g.hyp_stride = hyp_stride;
+  g.J = J;
+  g.ldj = ldj;
+  g.plane_stride = plane_stride;
+  g.j_bs = j_bstride;
+  adjoint_masks(*kd, g.adj_mask);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  GPK_HIP(timed(6, 0.0, 8.0 * (double)n * (double)m * kd->n_hyp * batch, s,
+                [&] { return launch_jacobian(*kd, g, X, x_bstride, n, Z, z_bstride, m, d, 0, batch, s); }),
+          "kernel_jacobian");
+  return 0;
+}
+
+size_t gpk_fisher_workspace_bytes(const gpk_kdesc* kd, const gpk_layout* lay) {
+  if (!kd || !lay || lay->n <= 0 || lay->m != lay->n || lay->batch <= 0 || lay->dtype != GPK_F64) return 0;
+  if (!valid_kdesc(kd, lay->d)) return 0;  // (gpk_fisher refuses such a program: no workspace to size)
+  return fisher_workspace_elems(kd->n_hyp, lay->n) * sizeof(double);
+}
+
+int gpk_fisher(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_dev, int64_t hyp_stride, const double* X,
+               int64_t x_bstride, const void* W, const int32_t* info_dev, double* fisher_dev, void* work,
+               size_t work_bytes, void* stream) {
+  if (check_layout(lay)) return fail_arg(2, "layout (use gpk_plan)");
+  if (lay->m != lay->n) return fail_arg(2, "gpk_fisher needs a layout planned with m = n");
+  if (lay->dtype != GPK_F64) return fail_arg(2, "Fisher information is fp64 only (layout planned with GPK_F32)");
+  if (!valid_kdesc(kd, lay->d)) return fail_arg(1, "kernel descriptor");
+  if (!hyp_dev && kd->n_hyp > 0) return fail_arg(3, "hyp_dev");
+  if (!X) return fail_arg(5, "X");
+  if (!W) return fail_arg(7, "W");
+  if (!info_dev) return fail_arg(8, "info_dev");
+  if (!fisher_dev) return fail_arg(9, "fisher_dev");
+  if (!work || work_bytes < gpk_fisher_workspace_bytes(kd, lay))
+    return fail_arg(11, "work (see gpk_fisher_workspace_bytes)");
+  FisherArgs g;
+  memset(&g, 0, sizeof(g));
+  g.W = static_cast<const double*>(W);
+  g.ld = lay->ld;
+  g.w_bs = lay->w_batch_stride;
+  g.n = lay->n;
+  g.n_pad = lay->n_pad;
+  g.d = (int32_t)lay->d;
+  g.hyp = hyp_dev;
+  g.hyp_stride = hyp_stride;
+  g.X = X;
+  g.x_bs = x_bstride;
+  g.info = info_dev;
+  g.fisher = fisher_dev;
+  g.work = static_cast<double*>(work);
+  adjoint_masks(*kd, g.adj_mask);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const double nn = (double)lay->n;
+  // (timing class 5, gpk_dgemm's: the products are the pass's flops)
+  GPK_HIP(timed(5, 2.0 * kd->n_hyp * nn * nn * nn * lay->batch, 0.0, s,
+                [&] { return launch_fisher(*kd, g, lay->batch, s); }),
+          "fisher");
+  return 0;
+}
+
 int gpk_mean_op_supported(int32_t op) {
   return (mean_leaf_hyp(op, 1) > 0 || op == GPK_MOP_ADD || op == GPK_MOP_MUL) ? 1 : 0;
 }

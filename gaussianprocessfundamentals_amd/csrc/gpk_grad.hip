@@ -1,6 +1,7 @@
 // Reverse mode of the kernel program: the LML gradient (gpk_nlml_grad: grad_kernel), the adjoints of a rectangular
 // kernel matrix (gpk_kernel_vjp: vjp_kernel) and the gradient of the held-out mean squared error (gpk_mse_backward:
-// mse_tile_kernel).  All walk 64 x 64 tiles staged as the K build stages them (gpk_stage.h) and re-evaluate the
+// mse_tile_kernel), and the forward planes d K / d theta_p written as matrices (gpk_kernel_jacobian: jacobian_kernel, at
+// the end, element-major: it reduces nothing and shares none of the three loops below).  All walk 64 x 64 tiles staged as the K build stages them (gpk_stage.h) and re-evaluate the
 // program per element with the reference's literal formulas (base_values, gpk_kernels.h).  launch_grad_cot runs
 // grad_kernel over a cotangent buffer instead of W's corner (the leave-one-out gradient, gpk_loo.hip): a host launcher,
 // launch_grad_tiles with five fields swapped.  The host side of the tile passes is said once (stage_args,
@@ -817,6 +818,86 @@ __global__ __launch_bounds__(256) void mse_reduce_kernel(MseArgs g, int64_t ntil
   }
 }
 
+// ================================================================================ derivative matrices
+// gpk_kernel_jacobian: the planes J[b][p][i][j] = d k(x_i, z_j) / d theta_p of K(X, Z), written instead of reduced.  One
+// 64 x 64 tile per workgroup (column tile blockIdx.x, row tile blockIdx.y, member blockIdx.z), staged as vjp_kernel
+// stages its tiles (rectangular, plain); lane = column, wave w = rows w, w + 4, ..., so a wave stores 64 consecutive
+// doubles of one row of a plane.  Per element the node values are evaluated once (programs with products), then every
+// leaf's base_partials runs with coef = its adjoint product over adj_mask and a zeroed acc, and the leaf's node_params
+// slots are stored to their planes (acc[GPK_MAX_DIM]: a moved sg, as in grad_kernel).  A bound shared by two adjacent
+// window leaves receives both contributions: the thread that owns the element adds the later leaf's to what it stored
+// for the earlier one (its own read-modify-write in program order: deterministic).  Every element of every plane of a
+// valid program is written, structural zeros included.  a0.uplo: tiles above the diagonal are skipped (gpk_fisher builds
+// the lower tiles of the symmetric X-against-X planes and mirrors them).  No reduction, no atomics.
+template <bool RQL>
+__global__ __launch_bounds__(256) void jacobian_kernel(gpk_kdesc kd, AsmArgs a0, JacArgs g) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  const int64_t ti = blockIdx.y, tj = blockIdx.x;
+  if (a0.uplo && tj > ti) return;  // (workgroup-uniform)
+  const int b = blockIdx.z;
+  AsmArgs a = a0;
+  a.X = a0.X + (int64_t)b * a0.x_bs;
+  a.Xs = a0.Xs + (int64_t)b * a0.xs_bs;
+  const int slot_stride = ATILE * a.dp;
+  double* hyp_s = smem;                                  // GPK_MAX_HYP
+  double* prow = hyp_s + GPK_MAX_HYP;
+  double* pcol = prow + (1 + kd.n_ard) * slot_stride;
+  double* vals = pcol + (1 + kd.n_ard) * slot_stride;    // [n_nodes][256] node values (MUL trees)
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const double* hyp_g = g.hyp + (int64_t)b * g.hyp_stride;
+  for (int e = tid; e < kd.n_hyp; e += 256) hyp_s[e] = hyp_g[e];
+  __syncthreads();
+  const int64_t gi0 = ti * ATILE, gj0 = tj * ATILE;
+  stage_points(kd, a, hyp_s, prow, gi0, 0, true, slot_stride);
+  stage_points(kd, a, hyp_s, pcol, gj0, 0, false, slot_stride);
+  __syncthreads();
+  const int c = lane;
+  const int64_t gj = gj0 + c;
+  if (gj >= a.m) return;  // (no barrier below)
+  double* J = g.J + (int64_t)b * g.j_bs;
+#pragma unroll 1
+  for (int k = 0; k < ATILE / 4; ++k) {
+    const int rr = wave + 4 * k;
+    const int64_t gi = gi0 + rr;
+    if (gi >= a.n) break;
+    if (g.has_mul) eval_nodes<RQL>(kd, hyp_s, prow + rr * a.dp, pcol + c * a.dp, slot_stride, a.d, vals + tid);
+    double* Je = J + gi * g.ldj + gj;
+#pragma unroll 1
+    for (int qn = 0; qn < kd.n_nodes; ++qn) {
+      const gpk_node nd = kd.nodes[qn];
+      if (nd.op == GPK_OP_ADD || nd.op == GPK_OP_MUL) continue;
+      const uint32_t mask = g.adj_mask[qn];
+      const int off = (nd.flags & GPK_NODE_ARD) ? (nd.ard_slot + 1) * slot_stride : 0;
+      double adj = 1.0;
+      if (mask != 0u) {
+#pragma unroll 1
+        for (int q = 0; q < kd.n_nodes; ++q)
+          if (mask & (1u << q)) adj *= vals[q * 256 + tid];
+      }
+      double acc[GNP];
+#pragma unroll
+      for (int s = 0; s < GNP; ++s) acc[s] = 0.0;
+      base_partials<RQL>(nd, hyp_s, prow + off + rr * a.dp, pcol + off + c * a.dp, a.d, adj, acc);
+      // hyperparameter slots of this node (node_params): ARD l_0..l_{d-1} then sg (stored at acc[GPK_MAX_DIM])
+      const bool vec = (nd.flags & GPK_NODE_ARD) != 0 || nd.op == GPK_OP_LIN;
+      const bool win = nd.op == GPK_OP_CPW;
+      const bool sg_moved = vec && (nd.flags & GPK_NODE_SCALED) != 0;
+      const int np = node_params(nd, a.d);
+#pragma unroll
+      for (int s = 0; s < GNP; ++s) {
+        if (s < np) {
+          const double v = (sg_moved && s == a.d) ? acc[GPK_MAX_DIM] : acc[s];
+          double* dst = Je + (int64_t)(nd.hyp_offset + s) * g.plane_stride;
+          // a bound shared with an earlier window leaf: add to what this thread stored for it
+          *dst = (win && cp_slot_written(kd, qn, nd.hyp_offset + s)) ? *dst + v : v;
+        }
+      }
+    }
+  }
+}
+
 }  // namespace
 
 int64_t mse_tiles(int64_t n, int64_t m) {
@@ -977,6 +1058,36 @@ hipError_t launch_grad_cot(const gpk_kdesc& kd, const GradArgs& g0, const double
   g.n_pad = 0;
   g.y_row = c_yrow;
   return launch_grad_tiles(kd, g0, g, GPK_F64, batch, s);
+}
+
+hipError_t launch_jacobian(const gpk_kdesc& kd, const JacArgs& g0, const double* X, int64_t x_bs, int64_t n,
+                           const double* Z, int64_t z_bs, int64_t m, int32_t d, int32_t lower_tiles, int32_t batch,
+                           hipStream_t s) {
+  if (kd.n_hyp == 0 || batch == 0) return hipSuccess;
+  AsmArgs a;
+  memset(&a, 0, sizeof(a));
+  a.X = X;
+  a.x_bs = x_bs;
+  a.Xs = Z;
+  a.xs_bs = z_bs;
+  a.n = n;
+  a.m = m;
+  a.d = d;
+  a.dp = padded_dim(d);
+  a.plain = 1;
+  a.uplo = lower_tiles;
+  JacArgs g = g0;
+  g.has_mul = 0;
+  for (int q = 0; q < kd.n_nodes; ++q) g.has_mul |= g.adj_mask[q] != 0u ? 1 : 0;
+  const int64_t tr = (n + ATILE - 1) / ATILE, tc = (m + ATILE - 1) / ATILE;
+  const size_t lds = sizeof(double) * (GPK_MAX_HYP + 2 * (size_t)(1 + kd.n_ard) * ATILE * a.dp +
+                                       (g.has_mul ? (size_t)kd.n_nodes * 256 : 0));
+  // (a program with a rational quadratic leaf: the instantiation that carries the leaf's code, rq_leaves)
+  const auto jac = rq_leaves(kd) > 0 ? jacobian_kernel<true> : jacobian_kernel<false>;
+  hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(jac), lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(jac, dim3((unsigned)tc, (unsigned)tr, (unsigned)batch), dim3(256), lds, s, kd, a, g);
+  return hipGetLastError();
 }
 
 }  // namespace gpk

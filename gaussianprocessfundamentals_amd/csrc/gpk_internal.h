@@ -299,6 +299,34 @@ struct VjpArgs {
   uint32_t adj_mask[GPK_MAX_NODES];
 };
 
+// gpk_kernel_jacobian (gpk_grad.hip): the planes d K(X, Z) / d theta_p, J[b][p][i][j] at J + b j_bs + p plane_stride + i ldj + j
+struct JacArgs {
+  const double* hyp;   // [batch][hyp_stride] device
+  int64_t hyp_stride;
+  double* J;
+  int64_t ldj, plane_stride, j_bs;
+  int32_t has_mul;     // set by launch_jacobian: some leaf has a MUL ancestor (node values are needed)
+  uint32_t adj_mask[GPK_MAX_NODES];
+};
+
+// gpk_fisher (gpk_fisher.hip): Fisher information of the hyperparameters and the noise from a factored
+// identity-augmented W (fp64), one member at a time through one workspace
+struct FisherArgs {
+  const double* W;     // corner -K^-1 (lower triangle)
+  int64_t ld;
+  int64_t w_bs;
+  int64_t n, n_pad;
+  int32_t d;
+  const double* hyp;
+  int64_t hyp_stride;
+  const double* X;
+  int64_t x_bs;
+  const int32_t* info;
+  double* fisher;      // [batch][n_hyp + 1][n_hyp + 1]
+  double* work;        // Q [n][n], D [n_hyp][n][n], T [n_hyp][n][n], part [pairs][tiles]
+  uint32_t adj_mask[GPK_MAX_NODES];
+};
+
 struct TrsvArgs {
   const void* W;
   int64_t ld;
@@ -341,6 +369,12 @@ hipError_t launch_mse_tiles(const gpk_kdesc& kd, const MseArgs& g, int32_t batch
 size_t vjp_workspace_elems(const gpk_kdesc& kd, int64_t n, int64_t m, int32_t d, bool want_z);
 hipError_t launch_vjp(const gpk_kdesc& kd, const VjpArgs& g, const double* X, int64_t n, const double* Z, int64_t m,
                       int32_t d, double* grad_hyp, double* grad_z, hipStream_t s);
+// the planes d K(X, Z) / d theta_p of ``batch`` members (Z member stride z_bs; lower_tiles: only tiles tj <= ti)
+hipError_t launch_jacobian(const gpk_kdesc& kd, const JacArgs& g, const double* X, int64_t x_bs, int64_t n,
+                           const double* Z, int64_t z_bs, int64_t m, int32_t d, int32_t lower_tiles, int32_t batch,
+                           hipStream_t s);
+size_t fisher_workspace_elems(int n_hyp, int64_t n);
+hipError_t launch_fisher(const gpk_kdesc& kd, const FisherArgs& g, int32_t batch, hipStream_t s);
 hipError_t launch_trsv_diag(const TrsvArgs& a, int dtype, int32_t batch, hipStream_t s);
 hipError_t launch_trsv_update(const TrsvArgs& a, int dtype, int32_t batch, hipStream_t s);
 hipError_t launch_gemv(const double* A, int64_t n, int64_t m, int64_t lda, const double* x, double* y,

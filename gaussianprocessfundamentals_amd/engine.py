@@ -484,7 +484,9 @@ class AugmentedFactorization:
         r = self._results.get(kind)
         if r is None:
             raise RuntimeError({"mse": "run_mse(...) or mse_gradient(...) first",
-                                "loo": "run_loo(...) or loo(...) first"}[kind])
+                                "loo": "run_loo(...) or loo(...) first", "fisher": "fisher() first"}[kind])
+        if kind == "fisher":   # (a matrix per member, not a read-out row: (F [B, n_hyp + 1, n_hyp + 1], None, info))
+            return r[0], None, self._info
         return r[0].view(self.batch, 4)[:, 0], r[1], self._info
 
     def run(self, kd: nat.GpkKdesc, hyp: torch.Tensor, hyp_stride: int, noise: torch.Tensor,
@@ -747,6 +749,7 @@ class InverseFactorization(_IdentityReadout, AugmentedFactorization):
         self._out = self._new(self.batch * 4)
         grad = self._new(self.batch, kd.n_hyp + 1) if gradient else None
         self._record("nlml", self._out, grad)
+        self._results.pop("fisher", None)   # (of an earlier run)
         self._check_operands(kd.n_hyp, hyp, hyp_stride, noise, noise_stride, X, x_bstride, y, y_bstride)
         work, work_bytes = None, 0
         if gradient:
@@ -811,6 +814,7 @@ class InverseFactorization(_IdentityReadout, AugmentedFactorization):
     def _run_loo_once(self, loss, kd, hyp, hyp_stride, noise, noise_stride, X, x_bstride, y, y_bstride, gradient):
         self._alphas = None
         self._record("nlml", self._out)   # (no -LML gradient of this run)
+        self._results.pop("fisher", None)
         out, mu, var, grad, work = self._loo_buffers(kd, gradient)
         self._check_operands(kd.n_hyp, hyp, hyp_stride, noise, noise_stride, X, x_bstride, y, y_bstride)
         nat.check(self.L.gpk_loo_grad(
@@ -833,6 +837,32 @@ class InverseFactorization(_IdentityReadout, AugmentedFactorization):
     def unsettled_loo(self):
         """(f, gradient, info) device views WITHOUT settling a pending persistent run (see unsettled_results)."""
         return self.results("loo", settle=False)
+
+    # -- Fisher information (gpk_fisher) ------------------------------------------------------------
+    def fisher(self) -> torch.Tensor:
+        """The Fisher information of the last :meth:`run` (gpk_fisher; W is only read): a device view
+        [B, n_hyp + 1, n_hyp + 1], F_pq = 1/2 tr(K^-1 d_pK K^-1 d_qK) with the hyperparameters in DFS order and the noise
+        last, enqueued without a host synchronisation (a pending persistent run is settled first, like every read of
+        W).  NaN for a member whose info != 0.  Recorded as the "fisher" results."""
+        if self.code != nat.GPK_F64:
+            raise NotImplementedError("Fisher information is fp64 only")
+        nat.require_fisher(self.L)
+        ops = self._loo_operands if self.done else None
+        if ops is None:
+            raise RuntimeError("run(...) first")
+        kd, hyp, hyp_stride, X, x_bstride = ops[:5]
+        self._settle()
+        need = int(self.L.gpk_fisher_workspace_bytes(ctypes.byref(kd), ctypes.byref(self.layout)))
+        if need == 0:
+            raise ValueError("the kernel program is not valid for dimension %d" % self.d)
+        work = self._workspace(need)
+        np1 = kd.n_hyp + 1
+        F = self._new(self.batch, np1, np1)
+        self._results["fisher"] = (F, None)
+        nat.check(self.L.gpk_fisher(ctypes.byref(kd), ctypes.byref(self.layout), nat.ptr(hyp), hyp_stride, nat.ptr(X),
+                                    x_bstride, nat.ptr(self._W), nat.ptr(self._info), nat.ptr(F), nat.ptr(work),
+                                    work.numel() * 8, nat.stream_handle(self._dev)), "gpk_fisher")
+        return F
 
     def gradient(self) -> torch.Tensor:
         """[batch, n_hyp + 1] fp64: d(-LML)/d hyp (DFS order), then d(-LML)/d noise."""
@@ -1353,6 +1383,26 @@ def kernel_vjp(kernel, hyper_parameter, X, Z, G: Optional[torch.Tensor] = None, 
                                nat.ptr(gh), nat.ptr(gz) if want_z else None, nat.ptr(work), wb,
                                nat.stream_handle(X.device)), "gpk_kernel_vjp")
     return gh[:kd.n_hyp], gz
+
+
+def kernel_jacobian(kernel, hyper_parameter, x, x_) -> torch.Tensor:
+    """The derivative matrices of K = kernel(x, x_) (gpk_kernel_jacobian): a device tensor [n_hyp, n, m] whose plane p
+    is d K / d (flat hyperparameter p, DFS order) -- the analytic derivatives kernel_vjp sums, every element written."""
+    L = nat.lib()
+    nat.require_fisher(L)
+    X = as_device_f64(x).contiguous()
+    Z = as_device_f64(x_).contiguous()
+    n, d = int(X.shape[0]), int(X.shape[1])
+    m = int(Z.shape[0])
+    kd = kernel_descriptor(kernel, d)
+    hyp = pack_hyper_parameter(hyper_parameter, kd.n_hyp)
+    J = torch.empty((kd.n_hyp, n, m), dtype=torch.float64, device=X.device)
+    if n == 0 or m == 0 or kd.n_hyp == 0:
+        return J
+    nat.check(L.gpk_kernel_jacobian(ctypes.byref(kd), nat.ptr(hyp), 0, 1, nat.ptr(X), n, 0, nat.ptr(Z), m, 0, d,
+                                    nat.ptr(J), m, n * m, kd.n_hyp * n * m, None, 0, nat.stream_handle(X.device)),
+              "gpk_kernel_jacobian")
+    return J
 
 
 def ski_weights(X: torch.Tensor, Z: torch.Tensor) -> torch.Tensor:

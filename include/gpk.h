@@ -516,6 +516,46 @@ int gpk_kernel_vjp(const gpk_kdesc* kd, const double* hyp_dev, const double* X, 
                    int32_t d, const double* G, int64_t ldg, const double* gu, const double* gv, double* grad_hyp,
                    double* grad_z, void* work, size_t work_bytes, void* stream);
 
+/* The derivative matrices of K = kernel(X, Z), written as planes (added without a new ABI number; look the symbols up
+ * like gpk_op_supported):
+ *   J[b*j_bstride + p*plane_stride + i*ldj + j] = d k(X_b,i, Z_b,j) / d hyp_b[p]   for p < n_hyp, i < n, j < m.
+ * X [batch][n, d] (member stride x_bstride), Z [batch][m, d] (z_bstride), hyp_dev [batch][n_hyp] (hyp_stride), all
+ * device fp64; a stride of 0 shares the operand between the members.  The derivatives are the analytic ones of the
+ * formulas the library evaluates, those gpk_kernel_vjp and gpk_nlml_grad sum: sign(l) for the Matern kernels' |l|, 0
+ * for the distance terms at coincident points, 0 for the hard change-point mask.  A change point shared by two windows
+ * holds the sum of both windows' terms.  Every element of every plane is written, structural zeros included, so J need
+ * not be cleared; nothing outside i < n, j < m is touched.  No reduction and no atomics: the same inputs give the same
+ * bits, and a member of a batch the bits of a single call.
+ * gpk_kernel_jacobian_workspace_bytes: bytes of `work` (host only); 0 -- the planes are written directly, and `work`
+ *   may be NULL.
+ * Errors: -1 invalid kernel program (or kd->dim != d), -2 hyp_dev, -3 hyp_stride, -4 batch (1 .. 65535), -5 X, -6 n,
+ *   -7 x_bstride, -8 Z, -9 m, -10 z_bstride, -11 d, -12 J, -13 ldj < m, -14 plane_stride < (n-1) ldj + m,
+ *   -15 j_bstride smaller than one member's planes.  n_hyp == 0 returns 0 and writes nothing. */
+size_t gpk_kernel_jacobian_workspace_bytes(const gpk_kdesc* kd, int64_t n, int64_t m, int32_t d);
+int gpk_kernel_jacobian(const gpk_kdesc* kd, const double* hyp_dev, int64_t hyp_stride, int32_t batch, const double* X,
+                        int64_t n, int64_t x_bstride, const double* Z, int64_t m, int64_t z_bstride, int32_t d,
+                        double* J, int64_t ldj, int64_t plane_stride, int64_t j_bstride, void* work, size_t work_bytes,
+                        void* stream);
+
+/* Fisher information of the hyperparameters and the noise (added without a new ABI number; fp64 only):
+ *   F_pq = 1/2 tr(K^-1 d_pK  K^-1 d_qK),  p, q <= n_hyp,  d_{n_hyp} K = d K / d noise = I,
+ * the expected Hessian of -LML, for every member of a layout planned with m = n whose W is factored as gpk_nlml_grad
+ * (or gpk_assemble_inverse + gpk_potrf_aug_ex(GPK_AUG_EXTRA_IDENTITY)) leaves it: the corner holds -K^-1.  W is only
+ * read.  hyp_dev, X: the operands of that factorisation.  fisher_dev[b*(n_hyp+1)^2 + p*(n_hyp+1) + q], hyperparameters
+ * in the program's order, the noise last; F_pq and F_qp are the same bits; the whole matrix of member b is NaN where
+ * info_dev[b] != 0.  Per member: K^-1 mirrored into a dense matrix, the planes d_pK (lower tiles of
+ * gpk_kernel_jacobian's kernel, mirrored: symmetric bit for bit), T_p = K^-1 d_pK on the f64 matrix cores (gpk_dgemm's
+ * kernel, 2 n_hyp n^3 flops), then 1/2 sum_ab T_p[a,b] T_q[b,a] per pair with fixed-order sums -- no atomics, the same
+ * inputs give the same bits.  Members are processed one after the other through the one workspace:
+ * gpk_fisher_workspace_bytes = 8 ((2 n_hyp + 1) n^2 + (n_hyp+1)(n_hyp+2)/2 ceil(n/64)^2) bytes, whatever the batch
+ *   (host only); 0 for an invalid kernel program, a layout planned with m != n or with GPK_F32.
+ * Errors: -1 invalid kernel program, -2 layout invalid, planned with m != n or with GPK_F32, -3 hyp_dev, -5 X, -7 W,
+ *   -8 info_dev, -9 fisher_dev, -11 work NULL or too small.  gpk_timing_read class 5 (gpk_dgemm's). */
+size_t gpk_fisher_workspace_bytes(const gpk_kdesc* kd, const gpk_layout* lay);
+int gpk_fisher(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_dev, int64_t hyp_stride, const double* X,
+               int64_t x_bstride, const void* W, const int32_t* info_dev, double* fisher_dev, void* work,
+               size_t work_bytes, void* stream);
+
 /* A[b] += value * I (the "+ tf.eye(n) * noise" of Nystroem_K.py:68-69 and
  * StructuredKernelInterpolation.py:27). */
 int gpk_add_diagonal(double* A, int64_t n, int64_t lda, int64_t a_bstride, int32_t batch, double value,

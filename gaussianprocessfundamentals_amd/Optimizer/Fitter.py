@@ -303,6 +303,28 @@ class DeviceLbfgsFitter(GradientFitter):
         return standard_errors_from_fisher(self.fisher_information().cpu(), free)
 
 
+    # -- after the fit: the model at new points --------------------------------------------------------
+    def predictor(self):
+        """A :class:`Statistics.Predictor.PosteriorPredictor` at the winning point of the last ``fit``: kernel
+        hyperparameters and noise from ``points[winner]``, one B = 1 identity-augmented factorisation of the training
+        data; ``predictor().predict(x_new, return_var=True)`` then streams any new points through it."""
+        name = type(self).__name__
+        if isinstance(self.data_input, list):
+            raise NotImplementedError("%s.predictor: the folds are a list of data inputs, there is no single "
+                                      "training set to predict from" % name)
+        if getattr(self, "points", None) is None:
+            raise RuntimeError("%s.predictor: fit() first" % name)
+        from ..Statistics.Predictor import PosteriorPredictor
+        kernel = self._kernel()
+        point = self.points[self.winner]
+        hyper_parameter = split_winner(point[:-1], kernel.get_hyper_parameter_dimensionalities())
+        mean_function = self._gp.mean_function
+        mean_hyp = mean_function.get_last_hyper_parameter()
+        if mean_hyp is None:
+            mean_hyp = mean_function.get_default_hyper_parameter()
+        return PosteriorPredictor(kernel, hyper_parameter, point[-1].clone(), mean_function, mean_hyp, self.data_input)
+
+
 def standard_errors_from_fisher(fisher, free) -> torch.Tensor:
     """sqrt(diag(F_free^-1)) scattered to all positions (host, fp64): NaN where ``free`` is false, inf for a free
     parameter whose row of F is zero (no information), the inverse taken over the remaining ones."""

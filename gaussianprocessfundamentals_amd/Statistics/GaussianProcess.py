@@ -75,6 +75,34 @@ class AbstractGaussianProcess:
             post_mu = self.aux.get_posterior_mu(kernel_hyper_param, noise)
         return mean_mu + post_mu, mean_mu, post_mu
 
+    def get_predictor(self, kernel_hyper_param: List = None, mean_function_hyper_param: List = None, noise=None):
+        """A :class:`Statistics.Predictor.PosteriorPredictor` over the training data of the data input: one
+        factorisation now, then ``predictor.predict(x_new)`` at any new points, as often as wanted, with a variance
+        (build extension).  The defaults are those of :meth:`predict`: last or default hyperparameters, noise = the
+        jitter p_cov_matrix_jitter."""
+        from ..DataHandling.DataInput import BatchDataInput
+        from .Predictor import PosteriorPredictor
+        name = type(self).__name__
+        if isinstance(self, _SegmentedGaussianProcess):
+            raise NotImplementedError("%s.get_predictor: segmented models are not supported" % name)
+        if self.data_input is None:
+            raise RuntimeError("%s.get_predictor: set_data_input(...) first" % name)
+        if isinstance(self.data_input, BatchDataInput):
+            raise NotImplementedError("%s.get_predictor: BatchDataInput is not supported" % name)
+        if noise is None:
+            noise = global_param.p_cov_matrix_jitter
+        if mean_function_hyper_param is None:
+            mean_function_hyper_param = self.mean_function.get_last_hyper_parameter()
+            if mean_function_hyper_param is None:
+                mean_function_hyper_param = self.mean_function.get_default_hyper_parameter()
+        if kernel_hyper_param is None:
+            kernel_hyper_param = self.kernel.get_last_hyper_parameter()
+            if kernel_hyper_param is None:
+                kernel_hyper_param = self.kernel.get_default_hyper_parameter(self.data_input.get_x_range(),
+                                                                             self.data_input.n_train)
+        return PosteriorPredictor(self.kernel, kernel_hyper_param, noise, self.mean_function,
+                                  mean_function_hyper_param, self.data_input)
+
     def get_n_prior_functions(self, n: int, hyper_param, noise, generator=None):
         """n prior function draws at the test points, [n_test, n] (GaussianProcess.py:87-95):
         L_K_ss N, N ~ normal(mean(y_train), std(y_train)) -- the reference's draw, whose mean and

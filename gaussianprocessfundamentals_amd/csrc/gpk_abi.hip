@@ -1956,6 +1956,59 @@ int gpk_fisher(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_dev
   return 0;
 }
 
+size_t gpk_predict_workspace_bytes(const gpk_kdesc* kd, const gpk_layout* lay, int64_t rows) {
+  if (!kd || !lay || lay->n <= 0 || lay->m != lay->n || lay->batch <= 0 || lay->dtype != GPK_F64) return 0;
+  if (lay->n_pad < lay->n || lay->n_pad % NB != 0 || rows < 1 || rows > predict_max_rows()) return 0;
+  if (!valid_kdesc(kd, lay->d)) return 0;  // (gpk_predict refuses such a program: no workspace to size)
+  return predict_workspace_elems(lay->n, lay->n_pad, rows) * sizeof(double);
+}
+
+int gpk_predict(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_dev, const double* X, const void* W,
+                int32_t member, const double* Xs, int64_t m, double* mu, double* var, void* work, size_t work_bytes,
+                void* stream) {
+  if (check_layout(lay)) return fail_arg(2, "layout (use gpk_plan)");
+  if (lay->m != lay->n) return fail_arg(2, "gpk_predict needs a layout planned with m = n");
+  if (lay->dtype != GPK_F64) return fail_arg(2, "prediction is fp64 only (layout planned with GPK_F32)");
+  if (!valid_kdesc(kd, lay->d)) return fail_arg(1, "kernel descriptor");
+  if (!hyp_dev && kd->n_hyp > 0) return fail_arg(3, "hyp_dev");
+  if (!X) return fail_arg(4, "X");
+  if (!W) return fail_arg(5, "W");
+  if (member < 0 || member >= lay->batch) return fail_arg(6, "member (0 .. batch - 1)");
+  if (!Xs) return fail_arg(7, "Xs");
+  if (m <= 0) return fail_arg(8, "m");
+  if (!mu && !var) return fail_arg(9, "mu and var (both NULL)");
+  // as many test points per pass as the workspace holds: all of them, or a multiple of the 64-row tile
+  const int64_t tile = std::min<int64_t>(m, ATILE);
+  if (!work || work_bytes < gpk_predict_workspace_bytes(kd, lay, tile))
+    return fail_arg(11, "work (see gpk_predict_workspace_bytes: at least one tile of 64 rows, or m rows)");
+  int64_t rows = (int64_t)(work_bytes / gpk_predict_workspace_bytes(kd, lay, 1));
+  rows = std::min<int64_t>(rows, predict_max_rows());
+  rows = rows >= m ? m : rows / ATILE * ATILE;
+  PredictArgs g;
+  memset(&g, 0, sizeof(g));
+  g.W = static_cast<const double*>(W) + (int64_t)member * lay->w_batch_stride;
+  g.ld = lay->ld;
+  g.n = lay->n;
+  g.n_pad = lay->n_pad;
+  g.y_row = lay->y_row;
+  g.d = (int32_t)lay->d;
+  g.hyp = hyp_dev;
+  g.X = X;
+  g.Xs = Xs;
+  g.m = m;
+  g.mu = mu;
+  g.var = var;
+  g.work = static_cast<double*>(work);
+  g.rows = rows;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const double nn = (double)lay->n;
+  // (timing class 5, gpk_dgemm's: the triangular product is the pass's flops)
+  GPK_HIP(timed(5, (var ? nn * nn : 0.0) * (double)m + 2.0 * nn * (double)m, 8.0 * nn * (double)m, s,
+                [&] { return launch_predict(*kd, g, s); }),
+          "predict");
+  return 0;
+}
+
 int gpk_mean_op_supported(int32_t op) {
   return (mean_leaf_hyp(op, 1) > 0 || op == GPK_MOP_ADD || op == GPK_MOP_MUL) ? 1 : 0;
 }

@@ -327,6 +327,23 @@ struct FisherArgs {
   uint32_t adj_mask[GPK_MAX_NODES];
 };
 
+// gpk_predict (gpk_predict.hip): posterior mean and latent variance at new points from one member of a factored
+// identity-augmented W (fp64), `rows` test points per pass through the workspace
+struct PredictArgs {
+  const double* W;     // the member's W: extra rows L^-T (upper triangle), the corner's y row -alpha^T
+  int64_t ld;
+  int64_t n, n_pad, y_row;
+  int32_t d;
+  const double* hyp;   // the member's hyperparameters
+  const double* X;     // the member's training points
+  const double* Xs;    // [m][d]
+  int64_t m;
+  double* mu;          // [m] or NULL
+  double* var;         // [m] or NULL
+  double* work;        // Ks' [rows][n_pad], kdiag [rows], part [ceil(n / 64)][rows]
+  int64_t rows;
+};
+
 struct TrsvArgs {
   const void* W;
   int64_t ld;
@@ -375,6 +392,9 @@ hipError_t launch_jacobian(const gpk_kdesc& kd, const JacArgs& g, const double* 
                            hipStream_t s);
 size_t fisher_workspace_elems(int n_hyp, int64_t n);
 hipError_t launch_fisher(const gpk_kdesc& kd, const FisherArgs& g, int32_t batch, hipStream_t s);
+int64_t predict_max_rows();  // test points per pass at most (a grid dimension)
+size_t predict_workspace_elems(int64_t n, int64_t n_pad, int64_t rows);
+hipError_t launch_predict(const gpk_kdesc& kd, const PredictArgs& g, hipStream_t s);
 hipError_t launch_trsv_diag(const TrsvArgs& a, int dtype, int32_t batch, hipStream_t s);
 hipError_t launch_trsv_update(const TrsvArgs& a, int dtype, int32_t batch, hipStream_t s);
 hipError_t launch_gemv(const double* A, int64_t n, int64_t m, int64_t lda, const double* x, double* y,

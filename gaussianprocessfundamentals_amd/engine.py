@@ -864,6 +864,57 @@ class InverseFactorization(_IdentityReadout, AugmentedFactorization):
                                     work.numel() * 8, nat.stream_handle(self._dev)), "gpk_fisher")
         return F
 
+    # -- prediction at new points from the kept factor (gpk_predict) ------------------------------------
+    PREDICT_WORK_BYTES = 256 << 20   # default bound of the prediction workspace (see predict)
+
+    def predict(self, Xs: torch.Tensor, want_var: bool = True, max_rows: Optional[int] = None, member: int = 0,
+                want_mu: bool = True):
+        """(mu [m], var [m] or None) device tensors at the new points ``Xs`` [m, d] from member ``member`` of the last
+        :meth:`run` (gpk_predict): mu = k(Xs, X) alpha in the units of the y that was factored, var the latent
+        posterior variance (no noise added).  Nothing is factored again and W is only read, so ``results("nlml")`` and
+        ``fisher()`` of the run stay what they were; enqueued without a host synchronisation (a pending persistent run
+        is settled first, like every read of W).  The caller checks ``info`` (:meth:`check_info`): the outputs of a
+        failed factorisation are meaningless.
+        The test points pass through the workspace ``max_rows`` at a time, 8 (n_pad + 1 + ceil(n / 64)) bytes each.
+        Default: as many as PREDICT_WORK_BYTES (256 MiB) hold, rounded down to a multiple of 64 and at least 64 -- 4032
+        rows at n = 8192 -- so the workspace stays bounded for any m; the result does not depend on it, bit for bit.
+        ``want_mu=False`` skips the mean (var only)."""
+        if self.code != nat.GPK_F64:
+            raise NotImplementedError("prediction is fp64 only")
+        nat.require_predict(self.L)
+        ops = self._loo_operands if self.done else None
+        if ops is None:
+            raise RuntimeError("run(...) first")
+        if not (want_mu or want_var):
+            raise ValueError("nothing to predict: want_mu and want_var are both off")
+        if not 0 <= int(member) < self.batch:
+            raise ValueError("member %d of a batch of %d" % (member, self.batch))
+        kd, hyp, hyp_stride, X, x_bstride = ops[:5]
+        Xs = as_device_f64(Xs)
+        if Xs.dim() != 2 or int(Xs.shape[1]) != self.d or int(Xs.shape[0]) < 1:
+            raise ValueError("Xs must be [m >= 1, %d], got %s" % (self.d, tuple(Xs.shape)))
+        Xs = Xs.contiguous()
+        m = int(Xs.shape[0])
+        self._settle()
+        lay = self.layout
+        per_row = int(self.L.gpk_predict_workspace_bytes(ctypes.byref(kd), ctypes.byref(lay), 1))
+        if per_row == 0:
+            raise ValueError("the kernel program is not valid for dimension %d" % self.d)
+        if max_rows is None:
+            max_rows = max(64, self.PREDICT_WORK_BYTES // per_row // 64 * 64)
+        elif int(max_rows) < 1:
+            raise ValueError("max_rows must be >= 1")
+        rows = min(m, max(min(m, 64), int(max_rows)))   # (the entry needs one tile of rows, or all of them)
+        work = self._workspace(rows * per_row)
+        mu = self._new(m) if want_mu else None
+        var = self._new(m) if want_var else None
+        nat.check(self.L.gpk_predict(ctypes.byref(kd), ctypes.byref(lay), _offset_ptr(hyp, member * hyp_stride),
+                                     _offset_ptr(X, member * x_bstride), nat.ptr(self._W), int(member), nat.ptr(Xs), m,
+                                     nat.ptr(mu), nat.ptr(var), nat.ptr(work), rows * per_row,
+                                     nat.stream_handle(self._dev)), "gpk_predict")
+        self._keep = (self._keep[0], Xs)
+        return mu, var
+
     def gradient(self) -> torch.Tensor:
         """[batch, n_hyp + 1] fp64: d(-LML)/d hyp (DFS order), then d(-LML)/d noise."""
         g = self.results("nlml")[1]

@@ -556,6 +556,31 @@ int gpk_fisher(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_dev
                int64_t x_bstride, const void* W, const int32_t* info_dev, double* fisher_dev, void* work,
                size_t work_bytes, void* stream);
 
+/* Posterior mean and latent variance at new points from a kept factorisation (added without a new ABI number; fp64
+ * only): for member `member` of a layout planned with m = n whose W is factored as gpk_nlml_grad (or
+ * gpk_assemble_inverse + gpk_potrf_aug_ex(GPK_AUG_EXTRA_IDENTITY)) leaves it -- L^-T in the extra rows, -alpha^T in the
+ * corner's y row -- and test points Xs [m, d]:
+ *   mu[c]  = sum_t k(xs_c, x_t) alpha_t                                     (S/Auxiliary.py:57-66)
+ *   var[c] = k(xs_c, xs_c) - sum_i (sum_{t <= i} k(xs_c, x_t) L^-1[i][t])^2   (the diagonal of S/Auxiliary.py:68-93)
+ * var is the latent variance: no noise is added.  k(xs_c, xs_c) is evaluated per test point (programs with a linear
+ * or a change-point window leaf are not stationary).  hyp_dev and X are the MEMBER's hyperparameters and training
+ * points (the caller adds member * stride); W is the batch's base pointer and is only read.  Either of mu / var may be
+ * NULL, not both.  The test points pass through `work` in chunks: as many per pass as work_bytes holds (all m, or a
+ * multiple of 64).  Per pass: k(Xs, X) of the chunk by gpk_kernel_matrix's launch (the same bits), mu by gpk_gemv's
+ * kernel, the row norms of the dense-times-triangular product on the f64 matrix cores (n^2 flops per test point; of
+ * the extra rows only the upper triangle of the training block is read), partial sums per 64 columns added in index
+ * order.  No atomics: the same inputs give the same bits, whatever the chunking.  info is not read: the caller checks
+ * it (the outputs of a failed factorisation are meaningless).
+ * gpk_predict_workspace_bytes = 8 rows (n_pad + 1 + ceil(n / 64)): the bytes one pass over `rows` test points needs,
+ *   1 <= rows <= 65535 * 64 (host only); 0 for an invalid kernel program, a layout planned with m != n or with GPK_F32.
+ * Errors: -1 invalid kernel program, -2 layout invalid, planned with m != n or with GPK_F32, -3 hyp_dev, -4 X, -5 W,
+ *   -6 member outside 0 .. batch - 1, -7 Xs, -8 m <= 0, -9 mu and var both NULL, -11 work NULL or smaller than
+ *   gpk_predict_workspace_bytes(kd, lay, min(m, 64)).  gpk_timing_read class 5 (gpk_dgemm's). */
+size_t gpk_predict_workspace_bytes(const gpk_kdesc* kd, const gpk_layout* lay, int64_t rows);
+int gpk_predict(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_dev, const double* X, const void* W,
+                int32_t member, const double* Xs, int64_t m, double* mu, double* var, void* work, size_t work_bytes,
+                void* stream);
+
 /* A[b] += value * I (the "+ tf.eye(n) * noise" of Nystroem_K.py:68-69 and
  * StructuredKernelInterpolation.py:27). */
 int gpk_add_diagonal(double* A, int64_t n, int64_t lda, int64_t a_bstride, int32_t batch, double value,

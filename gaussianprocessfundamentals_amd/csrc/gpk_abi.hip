@@ -285,6 +285,13 @@ thread_local ChainCtl t_chain_ctl;
 std::atomic<int64_t> g_chain_launches{0};      // persistent launches enqueued
 std::atomic<int64_t> g_chain_declined{0};      // auto mode: launch path taken, another stream busy
 std::atomic<int64_t> g_chain_force_timeout{0};  // testing: the next N persistent launches time out
+// gpk_tune "upd_tri" (GPK_UPD_TRI): uniform f64 128-tile group / half updates run their diagonal tiles (and the y
+// row's live block) as lower-triangle work in update_tri_kernel -- 1: after the strictly lower tiles, 2: before them,
+// 0: one gemm_kernel launch over all tiles.  The entry point's own knob, not a row of the knob table.
+std::atomic<int64_t>& upd_tri_knob() {
+  static std::atomic<int64_t> v{env_i64("GPK_UPD_TRI", 1)};
+  return v;
+}
 thread_local bool t_chain_last = false;         // this thread's last factorisation was the persistent one
 
 // Factorisations in flight per (device, stream): an event recorded on the caller's stream after every
@@ -629,6 +636,7 @@ static int potrf_impl(const gpk_layout* lay, void* W, void* Winv, int32_t* info_
   // one snapshot of the knobs per call: a gpk_tune from another thread (ctypes releases the GIL during
   // the enqueue) must not change the fuse decision between a panel's diag(k) and trsm(k)
   const Tune tn = tune_now();
+  const int64_t upd_tri = upd_tri_knob().load();
   t_chain_last = false;
   // a single evaluation: the whole factorisation as one persistent launch (no K build fused into it)
   if (!kb && chain_applies(lay, eye, n_dev, m_dev, tn, s)) {
@@ -731,8 +739,34 @@ static int potrf_impl(const gpk_layout* lay, void* W, void* Winv, int32_t* info_
         ga.y = kb->y;
         ga.y_bs = kb->y_bs;
       }
+      // upd_tri: a uniform f64 128-tile update of a group's trailing matrix goes out as two kernels inside the one
+      // counted launch -- gemm_kernel on the strictly lower tiles and update_tri_kernel on the lower 16 x 16 blocks of
+      // the diagonal tiles.  When the last tile row (the y row's) has a single live 16-row block, that row leaves
+      // gemm_kernel's grid too and each diagonal tile's workgroup takes its 8 blocks along (its B rows are staged
+      // there anyway).  Thin in-group updates (a 64-workgroup launch of its own would only serialise the stream),
+      // ragged and identity-augmented batches and the fused K build keep the single kernel.
+      const bool split = !solve && upd_tri != 0 && dt == GPK_F64 && st.tile == 128 && !eye && !n_dev &&
+                         st.row_end > 0 && !st.kbuild && st.bzn == 0 &&
+                         (st.role == LP_ROLE_GROUP || st.role == LP_ROLE_LOOKAHEAD || st.role == LP_ROLE_BULK ||
+                          st.role == LP_ROLE_HALF);
+      GemmArgs gt = ga;
+      if (split) {
+        const bool fold = st.row_end - (st.row0 + (st.nt - 1) * NB) <= 16;
+        gt.tri = fold ? 2 : 0;
+        ga.tri = 1;
+        if (fold) {
+          ga.nt = gt.nt - 1;
+          ga.c_hi = std::min(ga.c_hi, ga.nt);
+        }
+      }
       GPK_HIP(timed((int)st.cls, st.flops, st.bytes, q,
-                    [&] { return launch_gemm(ga, dt, solve ? GEMM_TRSM : GEMM_UPDATE, (int)st.tile, lay->batch, q); }),
+                    [&] {
+                      if (split && upd_tri == 2)  // (A/B: the diagonal tiles first)
+                        if (hipError_t e = launch_update_tri(gt, lay->batch, q)) return e;
+                      if (hipError_t e = launch_gemm(ga, dt, solve ? GEMM_TRSM : GEMM_UPDATE, (int)st.tile, lay->batch, q))
+                        return e;
+                      return split && upd_tri != 2 ? launch_update_tri(gt, lay->batch, q) : hipSuccess;
+                    }),
               solve ? "trsm" : update_label[st.role]);
     }
   }
@@ -2272,6 +2306,11 @@ int gpk_tune(const char* key, int64_t value, int64_t* old) {
   if (!key) return fail_arg(1, "key");
   if (!strcmp(key, "chain_force_timeout")) {  // (testing: the next `value` persistent launches time out)
     const int64_t prev = g_chain_force_timeout.exchange(value);
+    if (old) *old = prev;
+    return 0;
+  }
+  if (!strcmp(key, "upd_tri")) {
+    const int64_t prev = upd_tri_knob().exchange(value);
     if (old) *old = prev;
     return 0;
   }

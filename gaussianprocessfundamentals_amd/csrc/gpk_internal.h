@@ -114,6 +114,10 @@ struct GemmArgs {
   // evaluated -- k(x_i, x_j) + noise [i == j], identity padding, y row -- instead of loaded; the K
   // build then wrote only the panel columns of the first group
   int32_t band;    // update tile order: 0 row-major lower triangle, B > 0 bands of B tile rows
+  // the update split by tile class (gpk_tune "upd_tri").  gemm_kernel: 1 = the strictly lower tiles only.
+  // update_tri_kernel (launch_update_tri, the diagonal tiles of [c_lo, c_hi)): 2 = also the one live 16-row block
+  // of the last tile row (nt - 1, the y row's), which the caller then left out of gemm_kernel's nt
+  int32_t tri;
   int64_t row_end; // rows >= row_end are zero in every panel (0: unknown); MFMAs on them are skipped
   int32_t kbuild;
   int32_t d;
@@ -367,6 +371,8 @@ hipError_t launch_assemble(const gpk_kdesc& kd, const AsmArgs& a, int dtype, int
                            hipStream_t s);
 hipError_t launch_diag(const DiagArgs& a, int dtype, int32_t batch, hipStream_t s);
 hipError_t launch_gemm(const GemmArgs& a, int dtype, int mode, int tile, int32_t batch, hipStream_t s);
+// f64 update, 128-tiles: the lower 16 x 16 blocks of the diagonal tiles of [c_lo, c_hi) (gpk_update_tri.hip)
+hipError_t launch_update_tri(const GemmArgs& a, int32_t batch, hipStream_t s);
 hipError_t launch_finalize(const FinArgs& a, int dtype, int32_t batch, hipStream_t s);
 hipError_t launch_chain(const ChainArgs& a, int dtype, int grid, hipStream_t s);
 hipError_t chain_timeouts_read(int64_t* out);  // timed-out persistent launches on this device (synchronous)

@@ -20,37 +20,10 @@
 #include "gpk_diag_dev.h"
 #include "gpk_internal.h"
 #include "gpk_kernels.h"
+#include "gpk_tile_dev.h"
 
 namespace gpk {
 namespace {
-
-template <typename T>
-struct Mfma;
-template <>
-struct Mfma<double> {
-  typedef d4 acc_t;
-  static __device__ __forceinline__ acc_t op(double a, double b, acc_t c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-  }
-  // c - a b: on the f64 MFMA the blgp field is the neg modifier (neg:[1,0,0] negates A)
-  static __device__ __forceinline__ acc_t op_neg(double a, double b, acc_t c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 1);
-  }
-  // v_mfma_f64_16x16x4_f64 C/D map: col = lane & 15, row = (lane >> 4) + 4 * reg
-  static __device__ __forceinline__ int row(int lane, int reg) { return (lane >> 4) + 4 * reg; }
-};
-template <>
-struct Mfma<float> {
-  typedef f4 acc_t;
-  static __device__ __forceinline__ acc_t op(float a, float b, acc_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ acc_t op_neg(float a, float b, acc_t c) { return op(-a, b, c); }
-  // f32 16x16 C/D map: col = lane & 15, row = 4 * (lane >> 4) + reg
-  static __device__ __forceinline__ int row(int lane, int reg) { return 4 * (lane >> 4) + reg; }
-};
-
-typedef __attribute__((address_space(3))) void lds_void;
 
 // Waves along N of the 128 x 128 update tile: 2 (4 waves of 64 x 64 each) or 4 (8 waves of 64 x 32:
 // 111 VGPRs, so two 512-thread workgroups -- four waves per SIMD -- share a CU; f64 update +2.8 %)
@@ -65,8 +38,6 @@ typedef __attribute__((address_space(3))) void lds_void;
 #define GPK_ABLATE 0  // timing-only ablations of gemm_kernel (wrong results): 2 no epilogue, 3 K loop x2,
                       // 4 operands from one L2-resident block, 5 no per-chunk barrier (no C read: GPK_ABLATE_C)
 #endif
-
-constexpr int ROWB = 128;  // bytes of one row of a staged K chunk (8 pieces of 16 B)
 
 // bijective XCD-aware remap of the hardware block order (XCD = blockIdx % 8) to logical tiles.
 // run = 0: each XCD walks one contiguous run of tile ids, which share panel rows in its L2 (uniform
@@ -86,27 +57,6 @@ __device__ __forceinline__ int64_t xcd_remap(int64_t bid, int64_t nblk, int64_t 
   const int64_t x = bid % 8, pos = bid / 8;
   const int64_t base = (x < r) ? x * (q + 1) : r * (q + 1) + (x - r) * q;
   return base + pos;
-}
-
-// LDS image of a staged K chunk: one 128-B row per operand row, 16-B piece c of row r stored at
-// piece c ^ ((r >> 1) & 7).  The 16 rows a quarter-wave ds_read_b128 touches then fill all 16
-// slots of a 256-B bank row (conflict-free), while every global_load_lds wave-instruction still
-// writes its 1 KiB lane-linearly (8 rows): the swizzle is applied to the per-lane SOURCE address.
-__device__ __forceinline__ int swz(int r, int c) { return c ^ ((r >> 1) & 7); }
-
-// 16 B per lane global -> LDS (wave-uniform LDS base + 16 lane).  The gfx950 builtins sit in
-// __device__ helpers so that the host pass still emits the kernels' launch stubs.
-__device__ __forceinline__ void glds16(const void* src, void* lds_base) {
-  __builtin_amdgcn_global_load_lds(src, (lds_void*)lds_base, 16, 0, 0);
-}
-template <int AUX>  // cache-policy bits (16: sc1)
-__device__ __forceinline__ void glds16a(const void* src, void* lds_base) {
-  __builtin_amdgcn_global_load_lds(src, (lds_void*)lds_base, 16, 0, AUX);
-}
-__device__ __forceinline__ int wave_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-// LDS byte address of a pointer into shared memory (what M0 holds for an LDS DMA)
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-  return (unsigned)(unsigned long)(lds_void*)const_cast<void*>(p);
 }
 
 // buffer loads / stores of one element (voffset per lane, soffset wave-uniform)
@@ -330,10 +280,12 @@ __global__ __launch_bounds__(128 * WN, (WN == 4 && MODE == GEMM_UPDATE) ? 4 : 2)
   const int b = blockIdx.y;
   const int64_t t = xcd_remap(blockIdx.x, gridDim.x, a.nb != nullptr ? 8 : 0);
   int64_t ti, tj;  // tile coordinates in units of TM (rows) and TN (cols)
-  // tiles in row-major lower-triangle order, or banded (a.band > 0, gpk_tune("upd_band"))
+  // tiles in row-major lower-triangle order, or banded (a.band > 0, gpk_tune("upd_band")); a.tri = 1: the strictly
+  // lower tiles only (wt tile rows of the triangle, shifted down by one: update_tri_kernel has the diagonal tiles)
   if (MODE == GEMM_UPDATE) {
     const int64_t w = a.c_hi - a.c_lo;
-    const int64_t ttri = w * (w + 1) / 2;
+    const int64_t wt = w - a.tri;
+    const int64_t ttri = wt * (wt + 1) / 2;
     const int64_t B = a.band;
     if (t < ttri && B > 0) {
       // banded order: bands of B tile rows, each walked column by column, so that the tiles one XCD
@@ -341,13 +293,13 @@ __global__ __launch_bounds__(128 * WN, (WN == 4 && MODE == GEMM_UPDATE) ? 4 : 2)
       // B-panels in its L2 (row-major: 1 A- and 64 B-panels)
       int64_t q = 0, start = 0;
       for (;;) {
-        const int64_t h = (q * B + B <= w) ? B : w - q * B;
+        const int64_t h = (q * B + B <= wt) ? B : wt - q * B;
         const int64_t cnt = q * B * h + h * (h + 1) / 2;
         if (t < start + cnt) break;
         start += cnt;
         ++q;
       }
-      const int64_t h = (q * B + B <= w) ? B : w - q * B;
+      const int64_t h = (q * B + B <= wt) ? B : wt - q * B;
       int64_t u = t - start;
       int64_t r, c;
       if (u < q * B * h) {
@@ -363,13 +315,13 @@ __global__ __launch_bounds__(128 * WN, (WN == 4 && MODE == GEMM_UPDATE) ? 4 : 2)
         c = q * B + j;
         r = q * B + j + u;
       }
-      ti = a.c_lo + r;
+      ti = a.c_lo + a.tri + r;
       tj = a.c_lo + c;
     } else if (t < ttri) {
       int64_t r = (int64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
       while (r * (r + 1) / 2 > t) --r;
       while ((r + 1) * (r + 2) / 2 <= t) ++r;
-      ti = a.c_lo + r;
+      ti = a.c_lo + a.tri + r;
       tj = a.c_lo + (t - r * (r + 1) / 2);
     } else {
       const int64_t u = t - ttri;
@@ -801,8 +753,8 @@ hipError_t launch_gemm_t(const GemmArgs& a, int32_t batch, hipStream_t s) {
   // a.nt / c_lo / c_hi are in units of this launch's tile sizes
   unsigned nblk;
   if (MODE == GEMM_UPDATE) {
-    const int64_t w = a.c_hi - a.c_lo;
-    nblk = (unsigned)(w * (w + 1) / 2 + (int64_t)(a.nt - a.c_hi) * w);
+    const int64_t w = a.c_hi - a.c_lo, wt = w - a.tri;  // (tri: the strictly lower tiles, see gemm_kernel)
+    nblk = w <= 0 ? 0u : (unsigned)(wt * (wt + 1) / 2 + (int64_t)(a.nt - a.c_hi) * w);
   } else {
     nblk = (unsigned)a.nt;
   }

@@ -814,6 +814,11 @@ int gpk_timing_reset(void);
  * Stores the value and returns the previous one through *old (may be NULL); 0 or -1 (unknown
  * key).  Defaults come from the environment (GPK_LOOKAHEAD, GPK_RESERVE_CUS, ...). */
 int gpk_tune(const char* key, int64_t value, int64_t* old);
+/* One more gpk_tune key, the entry point's own like "chain_force_timeout" (process-wide only: gpk_tune_thread does not
+ * take it; default 1, environment GPK_UPD_TRI): "upd_tri" -- uniform f64 128-tile group / half trailing updates run
+ * their diagonal tiles and the y row's live 16-row block as lower-triangle work in a kernel of their own (1: after the
+ * strictly lower tiles, 2: before them, 0: one kernel over all tiles; bitwise identical results on and below the
+ * diagonal, the blocks above the diagonal of diagonal tiles are not written). */
 
 /* Per-host-thread override of a gpk_tune knob (no reference counterpart): set = 1 pins `value` for
  * the calls of the calling thread only, set = 0 removes the thread's override (the global knob applies

@@ -36,8 +36,20 @@ def main():
                   for r in csv.DictReader(open(path)))
     starts = [i for i, r in enumerate(rows) if "assemble_kernel" in r[2]]
     step = rows[starts[-1]:]
-    upd = [(s, e) for s, e, k in step if "gemm_kernel<double, 0" in k or "gemm_kernel<float, 0" in k]
     seq = sequence(n, batch, knobs)
+    # one span per update step: a group / half step may be two kernels (gpk_tune "upd_tri": gemm_kernel on the strictly
+    # lower tiles, then update_tri_kernel on the diagonal tiles; gemm_kernel is absent when no strictly lower tile is
+    # left) -- its span is the sum of the two durations
+    kern = [(s, e, "update_tri_kernel" in k) for s, e, k in step
+            if "gemm_kernel<double, 0" in k or "gemm_kernel<float, 0" in k or "update_tri_kernel" in k]
+    upd, i = [], 0
+    while i < len(kern):
+        s, e, tri = kern[i]
+        i += 1
+        if not tri and i < len(kern) and kern[i][2] and len(upd) < len(seq) and seq[len(upd)][0] != "thin":
+            e = e + (kern[i][1] - kern[i][0])
+            i += 1
+        upd.append((s, e))
     if len(seq) != len(upd):
         print("launch count mismatch: trace %d, plan %d (other knobs than the traced run's?)" % (len(upd), len(seq)))
     tot = {}

@@ -6,7 +6,9 @@ matrix of (n_pad + m + 1)^2 doubles.  :class:`PosteriorPredictor` runs ONE ident
 (engine.InverseFactorization: L^-T in the extra rows, -alpha in the corner's y row) and keeps it; every later
 :meth:`predict` is one pass of gpk_predict over the new points, linear in their number, in a bounded workspace, with
 the latent variance per point.  The formulas are the reference's (gpbasics/Statistics/Auxiliary.py:57-93):
-mu = K_s^T alpha, var = diag(K_ss) - |inv(L) K_s|^2 column-wise.
+mu = K_s^T alpha, var = diag(K_ss) - |inv(L) K_s|^2 column-wise.  The joint posterior comes from the same factor
+(DESIGN 28): :meth:`covariance` is K_ss - V^T V between new points (gpk_predict_vt + gpk_predict_cov), :meth:`sample`
+draws functions from it like get_n_posterior_functions (gpbasics/Statistics/GaussianProcess.py:97-110).
 """
 from __future__ import annotations
 
@@ -76,6 +78,57 @@ class PosteriorPredictor:
         if include_noise:
             var = var + self.noise
         return mean + mu, mean, mu, var
+
+    # -- the joint posterior: covariance between new points and function draws -----------------------
+    def covariance(self, x_new, x_other=None, include_noise: bool = False) -> torch.Tensor:
+        """The latent posterior covariance K_ss - V^T V between new points (Auxiliary.py:83-93, get_posterior_var),
+        from the kept factorisation: [m, m] of ``x_new`` with itself, symmetric bit for bit, or [m, m'] between
+        ``x_new`` and ``x_other``.  ``include_noise`` adds noise I (the covariance of observations at the points); it
+        has no meaning between two different sets of points."""
+        if include_noise and x_other is not None:
+            raise ValueError("include_noise adds noise I to the covariance of one set of points with itself: "
+                             "not with x_other")
+        x_new = self._points(x_new)
+        if x_other is not None:
+            return self.factorization.predict_cov(x_new, self._points(x_other))
+        sigma = self.factorization.predict_cov(x_new)
+        if include_noise:
+            engine.add_diagonal(sigma, float(self.noise[0]))
+        return sigma
+
+    def draw_factor(self, x_new, include_noise: bool = False):
+        """(mean + mu [m], L [m, m]) that :meth:`sample` draws from: L the lower Cholesky factor of
+        Sigma [+ noise I] + p_cov_matrix_jitter I on the device (engine.DenseFactorization; engine.CholeskyError if it
+        is not positive definite).  Keep it to draw again at the same points without factoring again."""
+        x_new = self._points(x_new)
+        total = self.predict(x_new)[0]
+        sigma = self.covariance(x_new, include_noise=include_noise)
+        f = engine.DenseFactorization(int(x_new.shape[0]))
+        f.run(sigma, float(torch.as_tensor(global_param.p_cov_matrix_jitter)))
+        f.check_info()
+        return total, f.cholesky(0).to(torch.float64).contiguous()
+
+    def sample(self, x_new, n_draws: int, generator=None, include_noise: bool = False, z=None) -> torch.Tensor:
+        """``n_draws`` posterior function draws at the new points, [m, n_draws] like get_n_posterior_functions
+        (GaussianProcess.py:97-110): mean + mu + chol(Sigma [+ noise I] + p_cov_matrix_jitter I) z, with
+        z ~ N(0, 1) [m, n_draws] from ``torch.randn`` on the device with ``generator`` unless ``z`` is given.
+        ``include_noise`` draws observations instead of latent function values."""
+        n_draws = int(n_draws)
+        if n_draws < 1:
+            raise ValueError("n_draws must be >= 1")
+        if z is not None:   # (checked before anything reaches the device)
+            z = z if isinstance(z, torch.Tensor) else torch.as_tensor(z)
+            m_given = int(len(x_new))
+            if tuple(z.shape) != (m_given, n_draws):
+                raise ValueError("z must be [%d, %d], got %s" % (m_given, n_draws, tuple(z.shape)))
+        x_new = self._points(x_new)
+        m = int(x_new.shape[0])
+        if z is not None:
+            z = engine.as_device_f64(z)
+        total, L = self.draw_factor(x_new, include_noise)
+        if z is None:
+            z = torch.randn((m, n_draws), dtype=torch.float64, device=L.device, generator=generator)
+        return engine.dgemm(L, z, beta=1.0, C=total.reshape(-1, 1).expand(m, n_draws).contiguous())
 
     def log_predictive_density(self, x_new, y_new) -> torch.Tensor:
         """Mean over the points of log N(y_new; mean + mu, var + noise) (rank 0, device)."""

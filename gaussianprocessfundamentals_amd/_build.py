@@ -22,7 +22,7 @@ LIB_NAME = "libgpk.so"
 LIB_PATH = os.path.join(HERE, LIB_NAME)
 SOURCES = ("gpk_assemble.hip", "gpk_grad.hip", "gpk_diag.hip", "gpk_potrf.hip", "gpk_approx.hip", "gpk_eig.hip",
            "gpk_flat.hip", "gpk_mean.hip", "gpk_fit.hip", "gpk_loo.hip", "gpk_fisher.hip", "gpk_predict.hip", "gpk_update_tri.hip",
-           "gpk_abi.hip",
+           "gpk_predict_cov.hip", "gpk_abi.hip",
            # host-only units: plain C++17 without a HIP header, built by the same hipcc line as the rest
            "gpk_tune.cpp", "gpk_chain_plan.cpp", "gpk_launch_plan.cpp")
 ARCH = "gfx950"

@@ -47,6 +47,7 @@ EXPORTS = (
     "gpk_loo_workspace_bytes", "gpk_loo_backward", "gpk_loo_grad",
     "gpk_kernel_jacobian_workspace_bytes", "gpk_kernel_jacobian", "gpk_fisher_workspace_bytes", "gpk_fisher",
     "gpk_predict_workspace_bytes", "gpk_predict",
+    "gpk_predict_vt_workspace_bytes", "gpk_predict_vt", "gpk_predict_cov",
 )
 # the ragged identity-augmented entries (added without a new ABI number, found by symbol)
 RAGGED_GRAD_ENTRIES = ("gpk_assemble_inverse_ragged", "gpk_potrf_aug_ragged_ex", "gpk_grad_ragged",
@@ -61,6 +62,8 @@ FISHER_ENTRIES = ("gpk_kernel_jacobian_workspace_bytes", "gpk_kernel_jacobian", 
                   "gpk_fisher")
 # the fitted predictor's pass over new points (likewise)
 PREDICT_ENTRIES = ("gpk_predict_workspace_bytes", "gpk_predict")
+# the joint posterior covariance at new points (likewise)
+PREDICT_COV_ENTRIES = ("gpk_predict_vt_workspace_bytes", "gpk_predict_vt", "gpk_predict_cov")
 
 
 class NativeUnavailable(RuntimeError):
@@ -213,10 +216,16 @@ def _declare(lib):
         "gpk_predict_workspace_bytes": (c_size_t, [POINTER(GpkKdesc), POINTER(GpkLayout), c_int64]),
         "gpk_predict": (c_int, [POINTER(GpkKdesc), POINTER(GpkLayout), P, P, P, c_int32, P, c_int64, P, P, P, c_size_t,
                                 P]),
+        "gpk_predict_vt_workspace_bytes": (c_size_t, [POINTER(GpkKdesc), POINTER(GpkLayout), c_int64]),
+        "gpk_predict_vt": (c_int, [POINTER(GpkKdesc), POINTER(GpkLayout), P, P, P, c_int32, P, c_int64, P, c_int64, P,
+                                   c_size_t, P]),
+        "gpk_predict_cov": (c_int, [POINTER(GpkKdesc), c_int32, P, P, c_int64, P, c_int64, P, c_int64, P, c_int64,
+                                    c_int64, P, c_int64, c_int32, P]),
     }
     for name, (res, args) in sig.items():
         if (name in ("gpk_op_supported", "gpk_launch_plan") or name in RAGGED_GRAD_ENTRIES or
                 name in MSE_GRAD_ENTRIES or name in LOO_ENTRIES or name in FISHER_ENTRIES or name in PREDICT_ENTRIES or
+                name in PREDICT_COV_ENTRIES or
                 name.startswith(("gpk_mean_", "gpk_fit_"))) and not hasattr(lib, name):
             continue  # (a library built before the entry existed: *op_supported() / fit_supported() then say no)
         fn = getattr(lib, name)
@@ -331,6 +340,20 @@ def require_predict(library=None):
     if not predict_supported(library):
         raise NativeUnavailable("this libgpk.so was built before the predictor entries (gpk_predict) existed: "
                                 "rebuild it")
+
+
+def predict_cov_supported(library=None) -> bool:
+    """Whether the library has the joint-covariance entries (gpk_predict_vt, its workspace query, gpk_predict_cov; added
+    without a new ABI number); False for one built before they existed -- it still loads, and the engine's
+    predict_vt / predict_cov calls raise NativeUnavailable."""
+    L = library if library is not None else load_library()
+    return all(hasattr(L, n) for n in PREDICT_COV_ENTRIES)
+
+
+def require_predict_cov(library=None):
+    if not predict_cov_supported(library):
+        raise NativeUnavailable("this libgpk.so was built before the joint-covariance entries (gpk_predict_vt, "
+                                "gpk_predict_cov) existed: rebuild it")
 
 
 def loo_loss_code(loss) -> int:

@@ -2043,6 +2043,107 @@ int gpk_predict(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_de
   return 0;
 }
 
+size_t gpk_predict_vt_workspace_bytes(const gpk_kdesc* kd, const gpk_layout* lay, int64_t rows) {
+  if (gpk_predict_workspace_bytes(kd, lay, rows) == 0) return 0;  // (the same refusals)
+  return predict_vt_workspace_elems(lay->n_pad, rows) * sizeof(double);
+}
+
+int gpk_predict_vt(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_dev, const double* X, const void* W,
+                   int32_t member, const double* Xs, int64_t m, double* Vt, int64_t ldv, void* work, size_t work_bytes,
+                   void* stream) {
+  if (check_layout(lay)) return fail_arg(2, "layout (use gpk_plan)");
+  if (lay->m != lay->n) return fail_arg(2, "gpk_predict_vt needs a layout planned with m = n");
+  if (lay->dtype != GPK_F64) return fail_arg(2, "prediction is fp64 only (layout planned with GPK_F32)");
+  if (!valid_kdesc(kd, lay->d)) return fail_arg(1, "kernel descriptor");
+  if (!hyp_dev && kd->n_hyp > 0) return fail_arg(3, "hyp_dev");
+  if (!X) return fail_arg(4, "X");
+  if (!W) return fail_arg(5, "W");
+  if (member < 0 || member >= lay->batch) return fail_arg(6, "member (0 .. batch - 1)");
+  if (!Xs) return fail_arg(7, "Xs");
+  if (m <= 0) return fail_arg(8, "m");
+  if (!Vt) return fail_arg(9, "Vt");
+  if (ldv < lay->n) return fail_arg(10, "ldv (at least n)");
+  // as many test points per pass as the workspace holds: all of them, or a multiple of the 64-row tile
+  const int64_t tile = std::min<int64_t>(m, ATILE);
+  if (!work || work_bytes < gpk_predict_vt_workspace_bytes(kd, lay, tile))
+    return fail_arg(11, "work (see gpk_predict_vt_workspace_bytes: at least one tile of 64 rows, or m rows)");
+  int64_t rows = (int64_t)(work_bytes / gpk_predict_vt_workspace_bytes(kd, lay, 1));
+  rows = std::min<int64_t>(rows, predict_max_rows());
+  rows = rows >= m ? m : rows / ATILE * ATILE;
+  PredictVtArgs g;
+  memset(&g, 0, sizeof(g));
+  g.W = static_cast<const double*>(W) + (int64_t)member * lay->w_batch_stride;
+  g.ld = lay->ld;
+  g.n = lay->n;
+  g.n_pad = lay->n_pad;
+  g.d = (int32_t)lay->d;
+  g.hyp = hyp_dev;
+  g.X = X;
+  g.Xs = Xs;
+  g.m = m;
+  g.V = Vt;
+  g.ldv = ldv;
+  g.work = static_cast<double*>(work);
+  g.rows = rows;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const double nn = (double)lay->n;
+  // (timing class 5, gpk_dgemm's: the triangular product is the pass's flops)
+  GPK_HIP(timed(5, nn * nn * (double)m, 8.0 * (2.0 * nn * (double)m + 0.5 * nn * nn), s,
+                [&] { return launch_predict_vt(*kd, g, s); }),
+          "predict_vt");
+  return 0;
+}
+
+int gpk_predict_cov(const gpk_kdesc* kd, int32_t d, const double* hyp_dev, const double* Xa, int64_t ma,
+                    const double* Va, int64_t lda, const double* Xb, int64_t mb, const double* Vb, int64_t ldb,
+                    int64_t n, double* C, int64_t ldc, int32_t symmetric, void* stream) {
+  if (d <= 0 || d > GPK_MAX_DIM) return fail_arg(2, "d");
+  if (!valid_kdesc(kd, d)) return fail_arg(1, "kernel descriptor");
+  if (!hyp_dev && kd->n_hyp > 0) return fail_arg(3, "hyp_dev");
+  if (symmetric != 0 && symmetric != 1) return fail_arg(15, "symmetric (0 or 1)");
+  if (n <= 0) return fail_arg(12, "n");
+  if (!Xa) return fail_arg(4, "Xa");
+  if (ma <= 0 || ma > predict_max_rows()) return fail_arg(5, "ma (1 .. 65535 * 64)");
+  // (the symmetric launch is one block per lower tile in grid.x: 256 threads each, fewer than 2^32 in all)
+  if (symmetric && (ma + ATILE - 1) / ATILE > 5792) return fail_arg(5, "ma (symmetric: at most 5792 * 64)");
+  if (!Va) return fail_arg(6, "Va");
+  if (lda < n) return fail_arg(7, "lda (at least n)");
+  if (!Xb) return fail_arg(8, "Xb");
+  if (symmetric && Xb != Xa) return fail_arg(8, "Xb (symmetric: Xb = Xa)");
+  if (mb <= 0 || mb > predict_max_rows()) return fail_arg(9, "mb (1 .. 65535 * 64)");
+  if (symmetric && mb != ma) return fail_arg(9, "mb (symmetric: mb = ma)");
+  if (!Vb) return fail_arg(10, "Vb");
+  if (symmetric && Vb != Va) return fail_arg(10, "Vb (symmetric: Vb = Va)");
+  if (ldb < n) return fail_arg(11, "ldb (at least n)");
+  if (symmetric && ldb != lda) return fail_arg(11, "ldb (symmetric: ldb = lda)");
+  if (!C) return fail_arg(13, "C");
+  if (ldc < mb) return fail_arg(14, "ldc (at least mb)");
+  PredictCovArgs g;
+  memset(&g, 0, sizeof(g));
+  g.hyp = hyp_dev;
+  g.d = d;
+  g.Xa = Xa;
+  g.ma = ma;
+  g.Va = Va;
+  g.lda = lda;
+  g.Xb = Xb;
+  g.mb = mb;
+  g.Vb = Vb;
+  g.ldb = ldb;
+  g.n = n;
+  g.C = C;
+  g.ldc = ldc;
+  g.symmetric = symmetric;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const double half = symmetric ? 0.5 : 1.0;
+  // (timing class 5, gpk_dgemm's)
+  GPK_HIP(timed(5, half * 2.0 * (double)ma * (double)mb * (double)n,
+                8.0 * (((double)ma + (double)mb) * (double)n + 2.0 * (double)ma * (double)mb), s,
+                [&] { return launch_predict_cov(*kd, g, s); }),
+          "predict_cov");
+  return 0;
+}
+
 int gpk_mean_op_supported(int32_t op) {
   return (mean_leaf_hyp(op, 1) > 0 || op == GPK_MOP_ADD || op == GPK_MOP_MUL) ? 1 : 0;
 }

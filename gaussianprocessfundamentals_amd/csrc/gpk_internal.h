@@ -348,6 +348,41 @@ struct PredictArgs {
   int64_t rows;
 };
 
+// gpk_predict_vt (gpk_predict_cov.hip): the rows V' = k(Xs, X) L^-T of new points from one member of a factored
+// identity-augmented W (fp64), `rows` test points per pass through the workspace
+struct PredictVtArgs {
+  const double* W;     // the member's W: extra rows L^-T (upper triangle)
+  int64_t ld;
+  int64_t n, n_pad;
+  int32_t d;
+  const double* hyp;   // the member's hyperparameters
+  const double* X;     // the member's training points
+  const double* Xs;    // [m][d]
+  int64_t m;
+  double* V;           // [m][ldv], columns < n written
+  int64_t ldv;
+  double* work;        // Ks' [rows][n_pad]
+  int64_t rows;
+};
+
+// gpk_predict_cov (gpk_predict_cov.hip): C = k(Xa, Xb) - Va Vb^T over the first n columns
+struct PredictCovArgs {
+  const double* hyp;
+  int32_t d;
+  const double* Xa;    // [ma][d]
+  int64_t ma;
+  const double* Va;    // [ma][lda]
+  int64_t lda;
+  const double* Xb;    // [mb][d]
+  int64_t mb;
+  const double* Vb;    // [mb][ldb]
+  int64_t ldb;
+  int64_t n;
+  double* C;           // [ma][ldc]
+  int64_t ldc;
+  int32_t symmetric;   // Xa = Xb, Va = Vb: lower tiles computed, mirrored
+};
+
 struct TrsvArgs {
   const void* W;
   int64_t ld;
@@ -401,6 +436,9 @@ hipError_t launch_fisher(const gpk_kdesc& kd, const FisherArgs& g, int32_t batch
 int64_t predict_max_rows();  // test points per pass at most (a grid dimension)
 size_t predict_workspace_elems(int64_t n, int64_t n_pad, int64_t rows);
 hipError_t launch_predict(const gpk_kdesc& kd, const PredictArgs& g, hipStream_t s);
+size_t predict_vt_workspace_elems(int64_t n_pad, int64_t rows);
+hipError_t launch_predict_vt(const gpk_kdesc& kd, const PredictVtArgs& g, hipStream_t s);
+hipError_t launch_predict_cov(const gpk_kdesc& kd, const PredictCovArgs& g, hipStream_t s);
 hipError_t launch_trsv_diag(const TrsvArgs& a, int dtype, int32_t batch, hipStream_t s);
 hipError_t launch_trsv_update(const TrsvArgs& a, int dtype, int32_t batch, hipStream_t s);
 hipError_t launch_gemv(const double* A, int64_t n, int64_t m, int64_t lda, const double* x, double* y,

@@ -915,6 +915,76 @@ class InverseFactorization(_IdentityReadout, AugmentedFactorization):
         self._keep = (self._keep[0], Xs)
         return mu, var
 
+    # -- the joint posterior covariance at new points (gpk_predict_vt, gpk_predict_cov) -----------------
+    def _predict_operands(self, member: int):
+        """(kd, the member's hyp pointer, the member's X pointer) of the last run, after the checks every pass over
+        new points shares."""
+        if self.code != nat.GPK_F64:
+            raise NotImplementedError("prediction is fp64 only")
+        nat.require_predict_cov(self.L)
+        ops = self._loo_operands if self.done else None
+        if ops is None:
+            raise RuntimeError("run(...) first")
+        if not 0 <= int(member) < self.batch:
+            raise ValueError("member %d of a batch of %d" % (member, self.batch))
+        kd, hyp, hyp_stride, X, x_bstride = ops[:5]
+        return kd, _offset_ptr(hyp, member * hyp_stride), _offset_ptr(X, member * x_bstride)
+
+    def _new_points(self, Xs, name: str) -> torch.Tensor:
+        Xs = as_device_f64(Xs)
+        if Xs.dim() != 2 or int(Xs.shape[1]) != self.d or int(Xs.shape[0]) < 1:
+            raise ValueError("%s must be [m >= 1, %d], got %s" % (name, self.d, tuple(Xs.shape)))
+        return Xs.contiguous()
+
+    def predict_vt(self, Xs: torch.Tensor, max_rows: Optional[int] = None, member: int = 0) -> torch.Tensor:
+        """V' = k(Xs, X) L^-T = (L^-1 K_s)^T at the new points ``Xs`` [m, d] from member ``member`` of the last
+        :meth:`run` (gpk_predict_vt): an [m, n] view of a new [m, n_pad] buffer, so that Sigma = K_ss - V' V'^T.
+        Settling, operand lifetimes and the workspace bound are those of :meth:`predict`: the points pass through
+        the workspace ``max_rows`` at a time, 8 n_pad bytes each, by default as many as PREDICT_WORK_BYTES hold; the
+        result does not depend on it, bit for bit.  W is only read."""
+        kd, hyp_p, X_p = self._predict_operands(member)
+        Xs = self._new_points(Xs, "Xs")
+        m = int(Xs.shape[0])
+        self._settle()
+        lay = self.layout
+        per_row = int(self.L.gpk_predict_vt_workspace_bytes(ctypes.byref(kd), ctypes.byref(lay), 1))
+        if per_row == 0:
+            raise ValueError("the kernel program is not valid for dimension %d" % self.d)
+        if max_rows is None:
+            max_rows = max(64, self.PREDICT_WORK_BYTES // per_row // 64 * 64)
+        elif int(max_rows) < 1:
+            raise ValueError("max_rows must be >= 1")
+        rows = min(m, max(min(m, 64), int(max_rows)))   # (the entry needs one tile of rows, or all of them)
+        work = self._workspace(rows * per_row)
+        Vt = self._new(m, lay.n_pad)
+        nat.check(self.L.gpk_predict_vt(ctypes.byref(kd), ctypes.byref(lay), hyp_p, X_p, nat.ptr(self._W), int(member),
+                                        nat.ptr(Xs), m, nat.ptr(Vt), lay.n_pad, nat.ptr(work), rows * per_row,
+                                        nat.stream_handle(self._dev)), "gpk_predict_vt")
+        self._keep = (self._keep[0], Xs)
+        return Vt[:, :self.n]
+
+    def predict_cov(self, Xa: torch.Tensor, Xb: Optional[torch.Tensor] = None, member: int = 0) -> torch.Tensor:
+        """The latent posterior covariance [ma, mb] between the new points ``Xa`` [ma, d] and ``Xb`` [mb, d] from
+        member ``member`` of the last :meth:`run`: k(Xa, Xb) - Va Vb^T with the rows of :meth:`predict_vt`
+        (gpk_predict_cov).  ``Xb=None`` is the symmetric mode, Sigma of ``Xa`` with itself: half the product's work,
+        symmetric bit for bit.  Nothing is factored again; enqueued without a host synchronisation."""
+        kd, hyp_p, _ = self._predict_operands(member)
+        Xa = self._new_points(Xa, "Xa")
+        Va = self.predict_vt(Xa, member=member)
+        symmetric = Xb is None
+        if symmetric:
+            Xb, Vb = Xa, Va
+        else:
+            Xb = self._new_points(Xb, "Xb")
+            Vb = self.predict_vt(Xb, member=member)
+        ma, mb, ld = int(Xa.shape[0]), int(Xb.shape[0]), int(self.layout.n_pad)
+        C = self._new(ma, mb)
+        nat.check(self.L.gpk_predict_cov(ctypes.byref(kd), self.d, hyp_p, nat.ptr(Xa), ma, nat.ptr(Va), ld,
+                                         nat.ptr(Xb), mb, nat.ptr(Vb), ld, self.n, nat.ptr(C), mb, int(symmetric),
+                                         nat.stream_handle(self._dev)), "gpk_predict_cov")
+        self._keep = (self._keep[0], (Xa, Xb, Va, Vb))
+        return C
+
     def gradient(self) -> torch.Tensor:
         """[batch, n_hyp + 1] fp64: d(-LML)/d hyp (DFS order), then d(-LML)/d noise."""
         g = self.results("nlml")[1]

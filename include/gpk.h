@@ -581,6 +581,40 @@ int gpk_predict(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_de
                 int32_t member, const double* Xs, int64_t m, double* mu, double* var, void* work, size_t work_bytes,
                 void* stream);
 
+/* The joint posterior covariance at new points from a kept factorisation (added without a new ABI number; fp64 only):
+ * the m x m matrix of S/Auxiliary.py:83-93 (get_posterior_var), the input of the draws of S/GaussianProcess.py:97-110
+ * (get_n_posterior_functions), without factoring again.  Two steps on the W that gpk_predict reads:
+ *   gpk_predict_vt:   Vt[c][i] = sum_{t <= i} k(xs_c, x_t) L^-1[i][t], i < n        (V' = (L^-1 K_s)^T, [m, n])
+ *   gpk_predict_cov:  C[a][b]  = k(xa_a, xb_b) - sum_{i < n} Va[a][i] Vb[b][i]       (Sigma = K_ss - V' V'^T, latent)
+ * gpk_predict_vt takes gpk_predict's arguments (hyp_dev and X the MEMBER's, W the batch's base pointer, only read) and
+ * passes the points through `work` in the same chunks; k(Xs, X) of a chunk is gpk_kernel_matrix's launch, the product
+ * runs on the f64 matrix cores in the 64 x 64 tiles of gpk_predict, and of the extra rows only the upper triangle of
+ * the training block is read.  It writes columns 0 .. n - 1 of each of the m rows of Vt (row stride ldv) and touches
+ * nothing else.  The same bits for any chunking and for any order of the points.
+ * gpk_predict_vt_workspace_bytes = 8 rows n_pad: the bytes one pass over `rows` test points needs; 0 under the
+ *   conditions of gpk_predict_workspace_bytes.
+ * Errors of gpk_predict_vt: -1 .. -8 as gpk_predict, -9 Vt NULL, -10 ldv < n, -11 work NULL or smaller than
+ *   gpk_predict_vt_workspace_bytes(kd, lay, min(m, 64)).
+ * gpk_predict_cov takes two sets of points with their rows of V' (Va [ma, lda], Vb [mb, ldb], columns >= n never
+ * read) and writes every element of C [ma, mb] (row stride ldc): k(Xa, Xb) by gpk_kernel_matrix's launch (the same
+ * bits), then per 64 x 64 tile the product summed over i in ascending order on the f64 matrix cores and subtracted
+ * from k in the epilogue.  symmetric = 1 (Xa = Xb, Va = Vb, ma = mb, lda = ldb -- the same pointers): only the tiles
+ * on or below the diagonal are computed and each element (a, b), a >= b, is written to (a, b) and to (b, a), so C is
+ * symmetric bit for bit (half the product's work).  No atomics; an element's bits do not depend on the tile or the
+ * block of points it sits in.  ma, mb <= 65535 * 64 (symmetric: 5792 * 64).
+ * Errors of gpk_predict_cov: -i for the i-th argument -- -1 invalid kernel program (or not of dimension d), -2 d
+ *   outside 1 .. GPK_MAX_DIM, -3 hyp_dev, -4 Xa, -5 ma, -6 Va, -7 lda < n, -8 Xb (symmetric: != Xa), -9 mb (symmetric:
+ *   != ma), -10 Vb (symmetric: != Va), -11 ldb < n (symmetric: != lda), -12 n <= 0, -13 C, -14 ldc < mb, -15 symmetric
+ *   not 0 or 1.
+ * Every argument error returns before any device work.  gpk_timing_read class 5 (gpk_dgemm's) for both. */
+size_t gpk_predict_vt_workspace_bytes(const gpk_kdesc* kd, const gpk_layout* lay, int64_t rows);
+int gpk_predict_vt(const gpk_kdesc* kd, const gpk_layout* lay, const double* hyp_dev, const double* X, const void* W,
+                   int32_t member, const double* Xs, int64_t m, double* Vt, int64_t ldv, void* work, size_t work_bytes,
+                   void* stream);
+int gpk_predict_cov(const gpk_kdesc* kd, int32_t d, const double* hyp_dev, const double* Xa, int64_t ma,
+                    const double* Va, int64_t lda, const double* Xb, int64_t mb, const double* Vb, int64_t ldb,
+                    int64_t n, double* C, int64_t ldc, int32_t symmetric, void* stream);
+
 /* A[b] += value * I (the "+ tf.eye(n) * noise" of Nystroem_K.py:68-69 and
  * StructuredKernelInterpolation.py:27). */
 int gpk_add_diagonal(double* A, int64_t n, int64_t lda, int64_t a_bstride, int32_t batch, double value,

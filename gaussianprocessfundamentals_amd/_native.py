@@ -497,7 +497,7 @@ def chain_plan(n_pad: int, y_row: int, grid: int, eye: bool = False, f32: bool =
 
 # One step of gpk_launch_plan (include/gpk.h: GPK_LAUNCH_STEP_WORDS 8-byte words, in this order)
 LAUNCH_STEP_WORDS = 23
-LAUNCH_KINDS = ("diag", "trsm", "update", "record", "wait")
+LAUNCH_KINDS = ("diag", "trsm", "update", "record", "wait", "prep")
 LAUNCH_STREAMS = ("caller", "panel", "bulk")
 LAUNCH_EVENTS = ("fork", "panel", "bulk", "join_p", "join_b")
 LAUNCH_ROLES = ("", "thin", "half", "look-ahead", "bulk", "group")

@@ -251,6 +251,30 @@ int32_t* fuse_counters(hipStream_t s) {
   return p;
 }
 
+// Operand scratch of the folded panel solves (the planner's in-group mode 4: prep_kernel writes it, the solve that
+// follows on the same stream reads it), one block per (device, stream) like the counters above and under the same
+// rule: no block for hipStreamPerThread or a stream being captured (the factorisation then keeps mode 3's steps).
+// Allocated at the stream's first folded factorisation, for the deepest operand of the batch and group size
+// (launch_fold_bytes), so one block serves every shape of that batch.  A larger batch or group later gets a new block
+// of at least twice the size; the old one is NOT freed: a thread that shares the stream may have fetched it and not
+// launched yet (the counters above never move either).  Owned for the life of the process.
+std::map<std::pair<int, hipStream_t>, std::pair<void*, size_t>> g_fold;
+
+void* fold_scratch(hipStream_t s, size_t bytes) {
+  if (s == hipStreamPerThread) return nullptr;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return nullptr;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+  std::lock_guard<std::mutex> lk(g_ctr_mu);
+  std::pair<void*, size_t>& blk = g_fold[{dev, s}];
+  if (blk.second >= bytes) return blk.first;
+  const size_t want = std::max(bytes, 2 * blk.second);
+  void* p = nullptr;
+  if (hipMalloc(&p, want) != hipSuccess) return nullptr;
+  blk = {p, want};  // (a previous, smaller block stays allocated, see above)
+  return p;
+}
 
 // ------------------------------------------------------------------------ persistent factorisation
 // The task list of one shape on the device (its order: chain_order, gpk_chain_plan.h), uploaded at the shape's
@@ -660,8 +684,17 @@ static int potrf_impl(const gpk_layout* lay, void* W, void* Winv, int32_t* info_
   int32_t* const ctr = (dt == GPK_F64 && tn.fuse_trsm) ? fuse_counters(sp) : nullptr;
 
   thread_local std::vector<LaunchStep> steps;  // (reused: no allocation per call once it has grown)
-  launch_plan({dt == GPK_F32, lay->batch, lay->m, lay->n_pad, lay->y_row, lay->p}, eye, ctr != nullptr, kb != nullptr,
-              tn, steps);
+  LaunchShape shape{dt == GPK_F32, lay->batch, lay->m, lay->n_pad, lay->y_row, lay->p, n_dev != nullptr, false};
+  launch_plan(shape, eye, ctr != nullptr, kb != nullptr, tn, steps);
+  // folded panel solves: their operand scratch on the panel stream, or the plan without them
+  void* wop = nullptr;
+  if (const int64_t fold_bytes = launch_fold_bytes(shape, eye, tn, steps)) {
+    wop = fold_scratch(sp, (size_t)fold_bytes);
+    if (!wop) {
+      shape.no_fold = true;
+      launch_plan(shape, eye, ctr != nullptr, kb != nullptr, tn, steps);
+    }
+  }
 
   DiagArgs dbase;
   memset(&dbase, 0, sizeof(dbase));
@@ -709,6 +742,21 @@ static int potrf_impl(const gpk_layout* lay, void* W, void* Winv, int32_t* info_
         da.ctr = ctr;
       }
       GPK_HIP(timed((int)st.cls, st.flops, st.bytes, q, [&] { return launch_diag(da, dt, lay->batch, q); }), "diag");
+    } else if (st.kind == LP_PREP) {  // the operand of the folded panel solve that follows on this stream
+      PrepArgs pa;
+      memset(&pa, 0, sizeof(pa));
+      pa.W = W;
+      pa.ld = lay->ld;
+      pa.w_bs = lay->w_batch_stride;
+      pa.Winv = Winv;
+      pa.inv_bs = lay->inv_batch_stride;
+      pa.kblk = st.kblk;
+      pa.j0 = st.j0;
+      pa.kdepth = (int32_t)st.kdepth;
+      pa.Wop = wop;
+      pa.ld_op = st.kdepth + NB;
+      pa.op_bs = NB * pa.ld_op;
+      GPK_HIP(timed((int)st.cls, st.flops, st.bytes, q, [&] { return launch_prep(pa, lay->batch, q); }), "prep");
     } else {
       GemmArgs ga = base;
       ga.j0 = st.j0;
@@ -725,6 +773,10 @@ static int potrf_impl(const gpk_layout* lay, void* W, void* Winv, int32_t* info_
       ga.row_end = st.row_end;
       const bool solve = st.kind == LP_TRSM;
       if (solve) ga.Binv = static_cast<const char*>(Winv) + (size_t)(st.j0 / NB) * NB * NB * es;
+      if (solve && st.kdepth > NB) {  // folded: against the PREP step's operand, K = kdepth contiguous per row
+        ga.Binv = wop;
+        ga.inv_bs = NB * st.kdepth;
+      }
       if (st.kbuild) {  // C is evaluated, not loaded (gpk_nlml's fused K build)
         ga.kbuild = 1;
         ga.d = kb->d;
@@ -2392,8 +2444,9 @@ int gpk_launch_plan(const gpk_layout* lay, int32_t flags, int32_t counters, int3
   if (!nsteps) return fail_arg(7, "nsteps");
   const Tune tn = tune_now();
   std::vector<LaunchStep> steps;
-  launch_plan({lay->dtype == GPK_F32, lay->batch, lay->m, lay->n_pad, lay->y_row, lay->p}, eye, counters != 0,
-              kbuild != 0, tn, steps);
+  // (a stream without the counters has no operand scratch either: fold_scratch's rule is fuse_counters')
+  launch_plan({lay->dtype == GPK_F32, lay->batch, lay->m, lay->n_pad, lay->y_row, lay->p, false, counters == 0}, eye,
+              counters != 0, kbuild != 0, tn, steps);
   *nsteps = (int64_t)steps.size();
   if (first_group) *first_group = launch_first_group(tn, eye, lay->n_pad);
   if (steps_out) {

@@ -92,7 +92,7 @@ struct GemmArgs {
   void* W;
   int64_t ld;
   int64_t w_bs;
-  const void* Binv;  // trsm: inverted diagonal block of this step
+  const void* Binv;  // trsm: inverted diagonal block of this step (folded: prep_kernel's operand, see below)
   int64_t inv_bs;
   int64_t j0;        // first column of the panel
   int64_t row0;      // first row (and column) of the trailing region
@@ -131,6 +131,23 @@ struct GemmArgs {
   int64_t x_bs;
   const double* y;
   int64_t y_bs;
+};
+// (The folded panel solve -- f64 trsm with kdepth > 128, the planner's in-group mode 4 -- takes no field of its own, so
+// that every other kernel's argument block stays what it was: X = [A | C] Wop^T over K = kdepth, the left operand's
+// columns [j0 + 128 - kdepth, j0 + 128) of W (the last 128 are the block column itself), the right operand
+// prep_kernel's: row n of member b at Binv + b inv_bs + n kdepth; stored in place at j0.)
+
+// prep_kernel (f64): per member Wop = [ -L_kk^-1 B | L_kk^-1 ] (128 x (kdepth + 128), row stride ld_op), B = W[128 kblk
+// .. + 127, j0 .. j0 + kdepth - 1], L_kk^-1 from Winv with exact zeros above the diagonal
+struct PrepArgs {
+  const void* W;
+  int64_t ld, w_bs;
+  const void* Winv;
+  int64_t inv_bs;
+  int64_t kblk, j0;
+  int32_t kdepth;
+  void* Wop;
+  int64_t ld_op, op_bs;
 };
 
 struct DiagArgs {
@@ -406,6 +423,7 @@ hipError_t launch_assemble(const gpk_kdesc& kd, const AsmArgs& a, int dtype, int
                            hipStream_t s);
 hipError_t launch_diag(const DiagArgs& a, int dtype, int32_t batch, hipStream_t s);
 hipError_t launch_gemm(const GemmArgs& a, int dtype, int mode, int tile, int32_t batch, hipStream_t s);
+hipError_t launch_prep(const PrepArgs& a, int32_t batch, hipStream_t s);
 // f64 update, 128-tiles: the lower 16 x 16 blocks of the diagonal tiles of [c_lo, c_hi) (gpk_update_tri.hip)
 hipError_t launch_update_tri(const GemmArgs& a, int32_t batch, hipStream_t s);
 hipError_t launch_finalize(const FinArgs& a, int dtype, int32_t batch, hipStream_t s);

@@ -118,15 +118,29 @@ struct Planner {
     out.push_back(s);
   }
 
-  // panel solve of block k: every row below the block (the y / test rows included)
-  void trsm(int64_t k, int stream) {
+  // the right operand of block column k's folded panel solve, from L_kk^-1 and block row k's columns [h0 NB, k NB):
+  // a triangular 128 x 128 times a 128 x 128 d product per member (its own flops, in the diagonal class)
+  void prep(int64_t k, int64_t h0, int stream) {
+    LaunchStep s = step(LP_PREP, stream, 1);
+    s.kblk = k;
+    s.j0 = h0 * NB;
+    s.row0 = k * NB;
+    s.kdepth = (k - h0) * NB;
+    s.flops = (double)sh.batch * NB * (NB + 1) * (double)s.kdepth;
+    out.push_back(s);
+  }
+
+  // panel solve of block k: every row below the block (the y / test rows included).  fold_depth > 0: the launch also
+  // applies the in-group update of the rows below the diagonal tile with the fold_depth columns left of the block
+  // (fold_flops: that update's algorithmic flops)
+  void trsm(int64_t k, int stream, int64_t fold_depth = 0, double fold_flops = 0.0) {
     if (fused_tiles(k) > 0) return;  // solved by the diagonal-block launch
     LaunchStep s = step(LP_TRSM, stream, 2);
     s.j0 = k * NB;
     s.row0 = s.j0 + NB;
     const int64_t rows = sh.p - s.row0;
     if (rows <= 0) return;
-    s.kdepth = NB;
+    s.kdepth = NB + fold_depth;
     s.row_end = tn.skip_zero_rows ? sh.y_row + 1 : 0;  // rows below the y row are zero
     if (eye) {  // identity rows t >= j0 + nb are still zero in this panel
       s.zlo = sh.n_pad + s.j0 + NB;
@@ -139,13 +153,16 @@ struct Planner {
     s.nt = b.compress(rows / s.tile);
     // algorithmic: rows that are nonzero in the panel (K part + extra rows) x nb^2
     const double rK = (double)(sh.n_pad - s.row0) + extra_nonzero(s.j0 + NB);
-    s.flops = (double)sh.batch * rK * NB * NB;
+    s.flops = (double)sh.batch * rK * NB * NB + fold_flops;
     out.push_back(s);
   }
 
   // trailing update from panel columns [j0, j0 + kdepth) of the lower tiles whose 128-column
-  // block lies in [c_lo, c_hi) (relative to row0 = j0 + kdepth; c_hi < 0: to the end)
-  void update(int64_t j0, int64_t kdepth, int64_t c_lo, int64_t c_hi, int stream, int role, bool fused_k = false) {
+  // block lies in [c_lo, c_hi) (relative to row0 = j0 + kdepth; c_hi < 0: to the end).  cap128 > 0: only the first
+  // cap128 block rows from row0 (the folded schedule's diagonal tile; plain layouts); returns the algorithmic flops of
+  // the rows the cap leaves out
+  double update(int64_t j0, int64_t kdepth, int64_t c_lo, int64_t c_hi, int stream, int role, bool fused_k = false,
+                int64_t cap128 = 0) {
     LaunchStep s = step(LP_UPDATE, stream, 3);
     s.role = role;
     s.kbuild = fused_k && kbuild;  // first trailing update: C is evaluated, not loaded (gpk_nlml's fused K build)
@@ -153,18 +170,19 @@ struct Planner {
     s.row0 = j0 + kdepth;
     s.kdepth = kdepth;
     s.row_end = tn.skip_zero_rows ? sh.y_row + 1 : 0;
-    const int64_t rows = sh.p - s.row0;
-    if (rows <= 0) return;
+    const int64_t rows_all = sh.p - s.row0;
+    if (rows_all <= 0) return 0.0;
+    const int64_t rows = cap128 > 0 ? std::min(rows_all, cap128 * NB) : rows_all;
     const int64_t t128 = rows / NB;
     if (c_hi < 0 || c_hi > t128) c_hi = t128;
-    if (c_lo >= c_hi) return;
+    if (c_lo >= c_hi) return 0.0;
     if (eye) {  // identity rows t >= j0 + kdepth are zero in the panel columns
       s.zlo = sh.n_pad + j0 + kdepth;
       s.zhi = sh.y_row;
     }
     const Band b128 = band_of(s, 128);
     const int64_t w128 = b128.compress(c_hi) - b128.compress(c_lo);
-    if (w128 <= 0) return;
+    if (w128 <= 0) return 0.0;
     const int64_t tiles128 = w128 * (w128 + 1) / 2 + (b128.compress(t128) - b128.compress(c_hi)) * w128;
     s.tile = (tiles128 * sh.batch >= tn.upd_t128_min) ? 128 : 64;
     const int64_t scale = NB / s.tile;
@@ -177,9 +195,11 @@ struct Planner {
     s.band = std::max<int64_t>(0, tn.upd_band);
     // algorithmic flops: 2 kdepth x (lower-triangle elements in the column range of the rows that
     // are nonzero in the panel: the K part, then the extra rows, which follow it contiguously)
-    const double rK = (double)(sh.n_pad - s.row0) + extra_nonzero(j0 + kdepth);
+    const double rK_all = (double)(sh.n_pad - s.row0) + extra_nonzero(j0 + kdepth);
+    const double rK = std::min(rK_all, (double)rows);
     const double cl = std::min(rK, (double)(c_lo * NB)), ch = std::min(rK, (double)(c_hi * NB));
     const double elems = (ch - cl) * rK - (cl + ch - 1.0) * (ch - cl) / 2.0;
+    const double elems_left_out = (ch - cl) * (rK_all - rK);  // (whole rows below the cap: cl, ch <= rK)
     // algorithmic bytes: the updated tiles' elements read + written once (y / test rows too)
     // and the panel rows read once
     const double es = sh.f32 ? 4.0 : 8.0;
@@ -189,6 +209,7 @@ struct Planner {
     s.flops = (double)sh.batch * 2.0 * kdepth * std::max(0.0, elems);
     s.bytes = (double)sh.batch * es * (2.0 * elems_all + rA * kdepth);
     out.push_back(s);
+    return (double)sh.batch * 2.0 * kdepth * std::max(0.0, elems_left_out);
   }
 
   void run() {
@@ -212,7 +233,16 @@ struct Planner {
     // group's, 36 instead of 42 panel-column reads + writes per group of 8 (they are HBM-bound).
     const int64_t rows128 = sh.p / NB;
     const bool right_looking = tn.ingroup == 2 || (tn.ingroup == 0 && sh.batch * rows128 < tn.rl_max_tiles);
-    const bool two_level = !right_looking && (tn.ingroup == 3 || tn.ingroup == 0) && G >= 4;
+    const bool two_level = !right_looking && (tn.ingroup == 3 || tn.ingroup == 4 || tn.ingroup == 0) && G >= 4;
+    // Folded columns (ingroup 4; f64 uniform plain batches): a column k of the two-level scheme with d = k - h0 > 0
+    // earlier panels in its half is not updated and then solved -- two launches that each stream the block column
+    // through HBM -- but solved against a deeper operand: with A the row tile's d earlier panels, B block row k's and C
+    // the row tile's part of column k,  (C - A B^T) L^-T = [A | C] [-L^-1 B | L^-1]^T.  Only the diagonal tile takes the
+    // thin update (diag(k) needs it); PREP forms the right operand once per member; the solve then runs at K = 128 (d +
+    // 1) over columns that lie contiguously in W.  d + 2 instead of d + 4 passes over the column, one launch of
+    // 64-row-tile grids less on the chain.  Same operations in another association: results agree with modes 1-3 to
+    // summation order, not bitwise.  Columns whose solve runs inside the diagonal launch keep mode 3's steps.
+    const bool fold = two_level && (tn.ingroup == 4 || tn.ingroup == 0) && !sh.f32 && !sh.ragged && !sh.no_fold && !eye;
     bool bulk_pending = false;
     for (int64_t g0 = 0, gsize = launch_first_group(tn, eye, sh.n_pad); g0 < nblk; g0 += gsize, gsize = G) {
       const int64_t gend = std::min(g0 + gsize, nblk);
@@ -220,6 +250,13 @@ struct Planner {
       for (int64_t k = g0; k < gend; ++k) {
         const int64_t h0 = k < gmid ? g0 : gmid;  // first panel of k's half
         if (two_level && k == gmid && gmid > g0) update(g0 * NB, (gmid - g0) * NB, 0, gend - gmid, sp, LP_ROLE_HALF);
+        if (fold && k > h0 && fused_tiles(k) == 0) {
+          const double rest = update(h0 * NB, (k - h0) * NB, 0, 1, sp, LP_ROLE_THIN, false, 1);
+          diag(k, sp);
+          prep(k, h0, sp);
+          trsm(k, sp, (k - h0) * NB, rest);
+          continue;
+        }
         if (!right_looking && k > h0) update(h0 * NB, (k - h0) * NB, 0, 1, sp, LP_ROLE_THIN);
         diag(k, sp);
         trsm(k, sp);
@@ -252,6 +289,14 @@ struct Planner {
 int64_t launch_first_group(const Tune& tn, bool eye, int64_t n_pad) {
   const int64_t G0 = std::max<int64_t>(1, std::min<int64_t>(tn.group_first, group_size(tn, eye)));
   return std::min<int64_t>(G0, n_pad / NB);
+}
+
+// (sized for the deepest operand any plan of this batch and group size can hold -- a half of ceil(G / 2) panels -- not
+// for this plan's own deepest, so that a stream's block does not grow from one shape to the next)
+int64_t launch_fold_bytes(const LaunchShape& sh, bool eye, const Tune& tn, const std::vector<LaunchStep>& steps) {
+  for (const LaunchStep& s : steps)
+    if (s.kind == LP_PREP) return sh.batch * NB * NB * ((group_size(tn, eye) + 1) / 2) * (int64_t)sizeof(double);
+  return 0;
 }
 
 void launch_plan(const LaunchShape& sh, bool eye, bool counters, bool kbuild, const Tune& tn,

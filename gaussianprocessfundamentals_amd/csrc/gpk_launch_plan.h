@@ -14,7 +14,9 @@ namespace gpk {
 
 constexpr int kFuseCtr = 256;  // ticket counters of the fused panel solve per stream: members per launch
 
-enum { LP_DIAG = 0, LP_TRSM = 1, LP_UPDATE = 2, LP_RECORD = 3, LP_WAIT = 4 };  // LaunchStep::kind
+// LaunchStep::kind.  PREP: the right operand of a folded panel solve (in-group mode 4, gpk_launch_plan.cpp), per member
+// Wop = [ -L_kk^-1 B | L_kk^-1 ], B = W[128 kblk .. + 127, j0 .. j0 + kdepth - 1], into the panel stream's scratch
+enum { LP_DIAG = 0, LP_TRSM = 1, LP_UPDATE = 2, LP_RECORD = 3, LP_WAIT = 4, LP_PREP = 5 };
 // LaunchStep::stream -- logical: with the look-ahead off every step is on the caller's stream; which queue the panel
 // stream is (gpk_tune "panel_stream") is the issuer's business
 enum { LP_CALLER = 0, LP_PANEL = 1, LP_BULK = 2 };
@@ -32,6 +34,10 @@ struct LaunchStep {
   // DIAG: block kblk (j0 = 128 kblk); trsm_tiles > 0: the panel solve of the 64-row tiles from row0 runs inside the
   // launch (no TRSM step follows), with the zero band [zlo, zhi)
   int64_t kblk, trsm_tiles;
+  // TRSM with kdepth > 128 (folded, in-group mode 4): block column j0 / 128 is updated with the kdepth - 128 columns
+  // left of it and solved in one launch -- X = [A | C] Wop^T over the columns [j0 + 128 - kdepth, j0 + 128), Wop the
+  // preceding PREP step's; flops: the solve's and the folded update's
+  // PREP: kblk, the B columns [j0, j0 + kdepth), row0 = 128 kblk
   // TRSM / UPDATE: panel columns [j0, j0 + kdepth), trailing region from row0; launch tile edge (128 / 64); nt tiles
   // of that edge from row0 and the update's tile-column range [c_lo, c_hi), both in the enumeration that leaves out
   // the bzn tiles from bz0 (the tiles wholly inside the zero band [zlo, zhi) of identity rows); tile order `band`;
@@ -46,7 +52,13 @@ static_assert(sizeof(LaunchStep) == kLaunchStepWords * 8, "LaunchStep is the rec
 struct LaunchShape {
   bool f32;
   int64_t batch, m, n_pad, y_row, p;
+  bool ragged = false;   // per-member sizes (gpk_potrf_aug_ragged): no folded panel solves
+  bool no_fold = false;  // the panel stream has no operand scratch (as for `counters`): no folded panel solves
 };
+
+// Bytes of the operand scratch a plan with folded panel solves needs (0: it has none): batch x 128 x 128 ceil(G / 2),
+// the deepest operand of the group size whatever the shape
+int64_t launch_fold_bytes(const LaunchShape& sh, bool eye, const Tune& tn, const std::vector<LaunchStep>& steps);
 
 // Whether the panel chain and the bulk updates run on side streams (look-ahead): the issuer needs the answer before
 // the plan, to create the streams and to find the panel stream's fuse counters

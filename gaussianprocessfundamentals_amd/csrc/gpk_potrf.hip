@@ -182,7 +182,8 @@ struct TileCore {
   };
 
   // One chunk of the K loop on the first MLIM row blocks: one basic block.  SOLVE: the panel solve (acc += a b
-  // against the lower-triangular inverse: K chunk kc feeds output columns >= kc GBK only); otherwise the update,
+  // against the lower-triangular inverse: K chunk ks feeds output columns >= ks GBK only; ks = kc except in the
+  // folded solve, kloop_fold_form); otherwise the update,
   // C first (acc -= a b).  Order inside a chunk: barrier, all
   // fragment reads, the MFMAs of the first half of the k-steps, THEN (GMID) the next chunk's global_load_lds,
   // then the second half.  hipcc's wait insertion treats an outstanding LDS DMA as pending LDS traffic and waits
@@ -197,13 +198,13 @@ struct TileCore {
 #define GPK_TILE_KSTEPS(S0, S1)                                                                               \
   _Pragma("unroll") for (int s = (S0); s < (S1); ++s)                                                         \
   _Pragma("unroll") for (int n = 0; n < NBK; ++n) {                                                           \
-    if (SOLVE && kc * GBK > f.wc * (TN / WN) + n * 16 + 15) continue;                                         \
+    if (SOLVE && ks * GBK > f.wc * (TN / WN) + n * 16 + 15) continue;                                         \
     _Pragma("unroll") for (int m = 0; m < MLIM; ++m)                                                          \
       acc[m][n] = SOLVE ? Mfma<T>::op(fa[m][s / EPC][s % EPC], fb[n][s / EPC][s % EPC], acc[m][n])            \
                         : Mfma<T>::op_neg(fa[m][s / EPC][s % EPC], fb[n][s / EPC][s % EPC], acc[m][n]);       \
   }
   template <int MLIM, bool SOLVE, bool BARRIER, typename Dma>
-  static __device__ __forceinline__ void chunk(Acc& acc, const char* smem, int NK, int kc, const Frag f,
+  static __device__ __forceinline__ void chunk(Acc& acc, const char* smem, int NK, int kc, int ks, const Frag f,
                                                const Dma& dma) {
     const int aoff = f.aoff, boff = f.boff, p0 = f.p0, p1 = f.p1;
     {
@@ -248,10 +249,34 @@ struct TileCore {
   template <int MLIM, bool SOLVE, bool BARRIER, typename Dma>
   static __device__ __forceinline__ void kloop_form(Acc& acc, const char* smem, int NK, const Frag f, const Dma& dma) {
     if (SOLVE) {
-      for (int kc = 0; kc < NK; ++kc) chunk<MLIM, SOLVE, BARRIER>(acc, smem, NK, kc, f, dma);
+      for (int kc = 0; kc < NK; ++kc) chunk<MLIM, SOLVE, BARRIER>(acc, smem, NK, kc, kc, f, dma);
     } else {
 #pragma nounroll
-      for (int kc = 0; kc < NK; ++kc) chunk<MLIM, SOLVE, BARRIER>(acc, smem, NK, kc, f, dma);
+      for (int kc = 0; kc < NK; ++kc) chunk<MLIM, SOLVE, BARRIER>(acc, smem, NK, kc, kc, f, dma);
+    }
+  }
+  // The folded panel solve (K = 128 (nd + 1)): first the 8 nd chunks of the earlier panels against -L^-1 B, a dense
+  // operand -- a rolled loop, no column skip (ks = 0) -- then the block column's own 8 chunks against L^-1, unrolled
+  // with the panel solve's skip of the zero upper 16-blocks (ks = the chunk's index within that part).
+  template <int MLIM, bool BARRIER, typename Dma>
+  static __device__ __forceinline__ void kloop_fold_form(Acc& acc, const char* smem, int nd, const Frag f,
+                                                         const Dma& dma) {
+    constexpr int NKB = NB / GBK;
+    const int NKA = nd * NKB, NK = NKA + NKB;
+#pragma nounroll
+    for (int kc = 0; kc < NKA; ++kc) chunk<MLIM, true, BARRIER>(acc, smem, NK, kc, 0, f, dma);
+#pragma unroll
+    for (int j = 0; j < NKB; ++j) chunk<MLIM, true, BARRIER>(acc, smem, NK, NKA + j, j, f, dma);
+  }
+  template <bool BARRIER, typename Dma>
+  static __device__ __forceinline__ void kloop_fold(Acc& acc, const char* smem, int nd, int mact, const Frag f,
+                                                    const Dma& dma) {
+    if (mact > 1) {
+      kloop_fold_form<MB, BARRIER>(acc, smem, nd, f, dma);
+    } else if (mact == 1) {
+      kloop_fold_form<1, BARRIER>(acc, smem, nd, f, dma);
+    } else {
+      kloop_fold_form<0, BARRIER>(acc, smem, nd, f, dma);
     }
   }
   // ... instantiated per MFMA row count (mact = MB, 1, 0 live 16-row blocks of this wave).  On entry chunk 0 is
@@ -269,8 +294,14 @@ struct TileCore {
   }
 };
 
-template <typename T, int MODE, int TM, int TN, int WN, int KB = 0>
+// FOLD (f64 panel solve only): the folded solve of the planner's in-group mode 4 -- K = a.kdepth over the columns
+// [j0 + 128 - kdepth, j0 + 128) of W, whose last 128 are the block column itself, against the operand prep_kernel
+// wrote (a.Binv, K = kdepth contiguous per row).  In place like the plain solve: a workgroup reads only its own rows
+// of the block column and columns to its left that no workgroup of the launch writes, and stores after its last chunk
+// has landed and been read.
+template <typename T, int MODE, int TM, int TN, int WN, int KB = 0, bool FOLD = false>
 __global__ __launch_bounds__(128 * WN, (WN == 4 && MODE == GEMM_UPDATE) ? 4 : 2) void gemm_kernel(GemmArgs a) {
+  static_assert(!FOLD || (MODE == GEMM_TRSM && sizeof(T) == 8 && KB == 0), "the folded form is an f64 panel solve");
   typedef TileCore<T, TM, TN, WN> Core;
   constexpr int EPC = Core::EPC, GBK = Core::GBK, WM = Core::WM, MB = Core::MB, NBK = Core::NBK;
   constexpr int STAGE = Core::STAGE, PW = Core::PW, RSTEP = Core::RSTEP;
@@ -341,7 +372,7 @@ __global__ __launch_bounds__(128 * WN, (WN == 4 && MODE == GEMM_UPDATE) ? 4 : 2)
   // structurally zero operand rows: the product (and so the update / solve) of the tile is zero
   if (zero_rows(a, b, R, R + TM)) return;
   if (MODE == GEMM_UPDATE && zero_rows(a, b, a.row0 + tj * TN, a.row0 + tj * TN + TN)) return;
-  const T* Ag = W + R * a.ld + a.j0;
+  const T* Ag = W + R * a.ld + (FOLD ? a.j0 + NB - a.kdepth : a.j0);
   const T* Bg;
   int64_t ldb;
   if (GPK_ABLATE == 4 && MODE == GEMM_UPDATE) {
@@ -351,6 +382,9 @@ __global__ __launch_bounds__(128 * WN, (WN == 4 && MODE == GEMM_UPDATE) ? 4 : 2)
   } else if (MODE == GEMM_UPDATE) {
     Bg = W + (a.row0 + tj * TN) * a.ld + a.j0;
     ldb = a.ld;
+  } else if (FOLD) {
+    Bg = reinterpret_cast<const T*>(a.Binv) + (int64_t)b * a.inv_bs;
+    ldb = a.kdepth;
   } else {
     Bg = reinterpret_cast<const T*>(a.Binv) + (int64_t)b * a.inv_bs;
     ldb = NB;
@@ -493,7 +527,7 @@ __global__ __launch_bounds__(128 * WN, (WN == 4 && MODE == GEMM_UPDATE) ? 4 : 2)
   const int aoff = (wr * (TM / WM) + lr) * ROWB;
   const int boff = (TM + wc * (TN / WN) + lr) * ROWB;
   const int p0 = swz(lr, q) * 16, p1 = swz(lr, q + 4) * 16;
-  const int NK0 = (MODE == GEMM_TRSM) ? NB / GBK : a.kdepth / GBK;
+  const int NK0 = (MODE == GEMM_TRSM && !FOLD) ? NB / GBK : a.kdepth / GBK;
   const int NK = (GPK_ABLATE == 3 && MODE == GEMM_UPDATE) ? 2 * NK0 : NK0;  // (ablation 3: twice over the same chunks)
   if (KB == 0) GPK_GLDS(0, 0);
   // 16-row blocks of this wave that hold a nonzero row: rows >= row_end (below the y row) are zero in
@@ -617,8 +651,12 @@ __global__ __launch_bounds__(128 * WN, (WN == 4 && MODE == GEMM_UPDATE) ? 4 : 2)
 #undef GPK_PIPE_GLDS_ASM
   } else {
     const auto dma = [=](int stage, int kc) __attribute__((always_inline)) { GPK_GLDS(stage, GPK_NEXT(kc)); };
-    Core::template kloop<MODE == GEMM_TRSM, BARRIER>(acc, smem, NK, mact, typename Core::Frag{wc, aoff, boff, p0, p1},
-                                                     dma);
+    if constexpr (FOLD)
+      Core::template kloop_fold<BARRIER>(acc, smem, a.kdepth / NB - 1, mact, typename Core::Frag{wc, aoff, boff, p0, p1},
+                                         dma);
+    else
+      Core::template kloop<MODE == GEMM_TRSM, BARRIER>(acc, smem, NK, mact,
+                                                       typename Core::Frag{wc, aoff, boff, p0, p1}, dma);
   }
 #undef GPK_NEXT
 #undef GPK_GLDS
@@ -748,7 +786,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const double* __restrict__ A,
   if (lane == 0) y[row] = alpha * sum + (beta == 0.0 ? 0.0 : beta * y[row]);
 }
 
-template <typename T, int MODE, int TM, int TN, int WN = 2, int KB = 0>
+template <typename T, int MODE, int TM, int TN, int WN = 2, int KB = 0, bool FOLD = false>
 hipError_t launch_gemm_t(const GemmArgs& a, int32_t batch, hipStream_t s) {
   // a.nt / c_lo / c_hi are in units of this launch's tile sizes
   unsigned nblk;
@@ -759,7 +797,7 @@ hipError_t launch_gemm_t(const GemmArgs& a, int32_t batch, hipStream_t s) {
     nblk = (unsigned)a.nt;
   }
   if (nblk == 0) return hipSuccess;
-  hipLaunchKernelGGL((gemm_kernel<T, MODE, TM, TN, WN, KB>), dim3(nblk, batch), dim3(128 * WN), 0, s, a);
+  hipLaunchKernelGGL((gemm_kernel<T, MODE, TM, TN, WN, KB, FOLD>), dim3(nblk, batch), dim3(128 * WN), 0, s, a);
   return hipGetLastError();
 }
 
@@ -1629,10 +1667,85 @@ __global__ __launch_bounds__(DT) void chain_kernel(ChainArgs a) {
   if (wave == 0) chain_trace(a, 1, 9);
 }
 
+// ================================================================================ folded solve's operand
+// prep_kernel: the right operand of a folded panel solve (planner's in-group mode 4), per member
+//   Wop = [ -L^-1 B | L^-1 ]   (128 rows, K = kdepth + 128 contiguous),
+// L^-1 = block kblk of Winv (lower triangular), B = W[128 kblk .. + 127, j0 .. j0 + kdepth - 1].  One workgroup per
+// (128-column block of B, member): 8 waves of 64 x 32, f64 MFMA 16 x 16 x 4, K in chunks of 16 staged through LDS
+// (row strides of 17 and 132 doubles keep the fragment reads off each other's banks).  K chunks right of a 16-row block
+// of L^-1 are zero and skipped.  The workgroup of the last block also copies L^-1 behind the product, with exact zeros
+// above the diagonal.  A small kernel (0.4 GF per member and factorisation at N = 8192), plain loads and stores.
+constexpr int PREP_LDA = 17, PREP_LDB = 132;
+__global__ __launch_bounds__(512) void prep_kernel(PrepArgs a) {
+  __shared__ double sa[NB * PREP_LDA];  // L^-1[0..127, t0 .. t0 + 15]
+  __shared__ double sb[16 * PREP_LDB];  // B[t0 .. t0 + 15, 0..127] of this column block
+  const int blk = blockIdx.x, b = blockIdx.y;
+  const int nblk = a.kdepth / NB;
+  const double* Li = reinterpret_cast<const double*>(a.Winv) + (int64_t)b * a.inv_bs + a.kblk * (int64_t)(NB * NB);
+  const double* Bm = reinterpret_cast<const double*>(a.W) + (int64_t)b * a.w_bs + a.kblk * NB * a.ld + a.j0 +
+                     (int64_t)blk * NB;
+  double* Wo = reinterpret_cast<double*>(a.Wop) + (int64_t)b * a.op_bs;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int wr = wid >> 2, wc = wid & 3;  // 64 rows x 32 columns per wave
+  const int lr = lane & 15, q = lane >> 4;
+  d4 acc[4][2];
+#pragma unroll
+  for (int m = 0; m < 4; ++m)
+#pragma unroll
+    for (int n = 0; n < 2; ++n) acc[m][n] = d4{0, 0, 0, 0};
+  const int ar = tid >> 2, ac = (tid & 3) * 4;    // this thread's 4 elements of the L^-1 chunk
+  const int br = tid >> 5, bc = (tid & 31) * 4;   // ... and of the B chunk
+  for (int t0 = 0; t0 < NB; t0 += 16) {
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      sa[ar * PREP_LDA + ac + e] = t0 + ac + e <= ar ? Li[ar * NB + t0 + ac + e] : 0.0;
+      sb[br * PREP_LDB + bc + e] = Bm[(int64_t)(t0 + br) * a.ld + bc + e];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      const int n0 = wr * 64 + m * 16;
+      if (n0 + 15 < t0) continue;  // L^-1[n, t] = 0 for t > n
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const double av = sa[(n0 + lr) * PREP_LDA + s * 4 + q];
+#pragma unroll
+        for (int n = 0; n < 2; ++n)
+          acc[m][n] = Mfma<double>::op_neg(av, sb[(s * 4 + q) * PREP_LDB + wc * 32 + n * 16 + lr], acc[m][n]);
+      }
+    }
+  }
+#pragma unroll
+  for (int m = 0; m < 4; ++m)
+#pragma unroll
+    for (int n = 0; n < 2; ++n)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        Wo[(int64_t)(wr * 64 + m * 16 + Mfma<double>::row(lane, r)) * a.ld_op + (int64_t)blk * NB + wc * 32 + n * 16 + lr] =
+            acc[m][n][r];
+  if (blk == nblk - 1) {
+    for (int i = tid; i < NB * NB; i += 512) {
+      const int n = i >> 7, j = i & (NB - 1);
+      Wo[(int64_t)n * a.ld_op + a.kdepth + j] = j <= n ? Li[i] : 0.0;
+    }
+  }
+}
+
 }  // namespace
+
+hipError_t launch_prep(const PrepArgs& a, int32_t batch, hipStream_t s) {
+  if (a.kdepth < NB || a.kdepth % NB != 0 || a.ld_op < a.kdepth + NB) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(prep_kernel, dim3((unsigned)(a.kdepth / NB), batch), dim3(512), 0, s, a);
+  return hipGetLastError();
+}
 
 #ifndef GPK_TRSM_WN
 #define GPK_TRSM_WN 2  // waves along N of the f64 128-tile TRSM (4: the update's 8-wave 64 x 32 layout)
+#endif
+
+#ifndef GPK_FOLD_WN
+#define GPK_FOLD_WN 2  // waves along N of the folded 128-tile solve (4: the update's 8-wave 64 x 32 layout)
 #endif
 
 hipError_t launch_gemm(const GemmArgs& a, int dtype, int mode, int tile, int32_t batch, hipStream_t s) {
@@ -1656,6 +1769,16 @@ hipError_t launch_gemm(const GemmArgs& a, int dtype, int mode, int tile, int32_t
     if (mode == GEMM_UPDATE)
       return tile == 128 ? launch_gemm_t<double, GEMM_UPDATE, 128, 128, GPK_UPD_WN>(a, batch, s)
                          : launch_gemm_t<double, GEMM_UPDATE, 64, 64>(a, batch, s);
+    // The folded solve (in-group mode 4) has no argument of its own (profiles/ingroup_fold_codegen.txt): an f64 panel
+    // solve with kdepth > 128 IS the folded one.  The invariant that ties the three places together:
+    //   TRSM kdepth  ==  PREP kdepth + 128  ==  row stride of the operand (PrepArgs::ld_op; Binv's rows here),
+    // with inv_bs = 128 x that stride (potrf_impl sets both from the plan's steps) and the left operand's first
+    // column j0 + 128 - kdepth (gemm_kernel).
+    if (a.kdepth > NB) {
+      if (a.Binv == nullptr || a.kdepth % NB != 0 || a.kdepth > a.j0 + NB) return hipErrorInvalidValue;
+      return tile == 128 ? launch_gemm_t<double, GEMM_TRSM, 128, 128, GPK_FOLD_WN, 0, true>(a, batch, s)
+                         : launch_gemm_t<double, GEMM_TRSM, 64, 128, 2, 0, true>(a, batch, s);
+    }
     return tile == 128 ? launch_gemm_t<double, GEMM_TRSM, 128, 128, GPK_TRSM_WN>(a, batch, s)
                        : launch_gemm_t<double, GEMM_TRSM, 64, 128>(a, batch, s);
   }

@@ -29,7 +29,9 @@
   K(skip_zero_rows, 1)     /* skip the MFMAs of the all-zero 16-row blocks below the y row */                          \
   K(syevj_abs_tol_e3, 0)   /* Jacobi: absolute rotation threshold in units of 1e-3 eps max|a_ii| */                    \
   K(diag_version, 2)       /* diagonal-block kernel: 2 look-ahead schedule, 1 phase-serial */                          \
-  K(ingroup, 0)            /* in-group updates: 1 left-looking, 2 right-looking, 3 two-level, 0 auto (by batch) */     \
+  K(ingroup, 0)            /* in-group updates: 1 left-looking, 2 right-looking, 3 two-level, 4 two-level with the     \
+                              columns' updates folded into their panel solves (uniform f64 plain batches; else 3),     \
+                              0 auto (by batch: 2 or 4) */                                                             \
   K(rl_max_tiles, 256)     /* auto: right-looking while batch x (block rows) stays below this */                       \
   K(band_skip, 1)          /* identity extra rows: leave the zero band's tiles out of the grid */                      \
   K(group_eye, 4)          /* panels per trailing update of identity-augmented factorisations */                       \

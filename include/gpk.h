@@ -767,7 +767,12 @@ int gpk_fit_current(int n_par, int batch, const double* state_dev, double* x_dev
                     double* g_dev, int64_t g_stride, int32_t* iters_dev, void* stream);
 
 /* Per-kernel-class timing with HIP events recorded on the launch stream.
- * class: 0 assemble, 1 diag, 2 trsm, 3 update, 4 finalize, 5 trsv, 6 grad */
+ * class: 0 assemble, 1 diag, 2 trsm, 3 update, 4 finalize, 5 trsv, 6 grad.
+ * With folded columns (gpk_tune "ingroup" 4) the classes of a factorisation shift: a folded panel solve carries its
+ * column's in-group update in class 2 (those flops leave class 3), and class 1 also holds the launches that form the
+ * folded solves' operands with their 128 * 129 * 128 d flops per member and column -- work the algorithm does not
+ * have, so class 1's flops (and the classes' total) exceed the closed form of the factorisation by exactly that, and a
+ * class 1 rate is no longer that of the diagonal-block kernel alone. */
 #define GPK_NUM_CLASSES 7
 int gpk_timing_enable(int on);
 /* synchronises the recorded events; returns totals since the last reset */
@@ -788,8 +793,14 @@ int gpk_timing_reset(void);
  * "upd_band" (trailing-update tile order), "skip_zero_rows" (skip the MFMAs of the zero rows below
  * the y row), "upd_t128_min", "trsm_t128_min" (128-tile thresholds), "diag_version" (2: look-ahead
  * diagonal-block kernel, 1: the phase-serial one; bitwise identical results), "ingroup" (in-group
- * updates: 0 auto, 1 left-looking, 2 right-looking, 3 two-level left-looking) with "rl_max_tiles"
- * (auto picks right-looking while batch x block rows stays below it, two-level otherwise),
+ * updates: 0 auto, 1 left-looking, 2 right-looking, 3 two-level left-looking, 4 two-level with folded columns -- a
+ * column with earlier panels in its half is updated and solved by ONE panel-solve launch against the operand
+ * [-L^-1 B | L^-1]; uniform f64 batches without identity rows, where the panel solve is a launch of its own and the
+ * panel stream can hold the operand scratch -- not hipStreamPerThread and not a stream being captured, the condition
+ * of the fused panel solve's counters; everywhere else 4 runs 3, so a captured call and the same call made eagerly
+ * agree to summation order (about 1e-14 relative on -LML), not bit for bit, unless "ingroup" is set to 1-3; results
+ * agree with 1-3 to summation order, not bitwise) with "rl_max_tiles"
+ * (auto picks right-looking while batch x block rows stays below it, the folded two-level form otherwise),
  * "band_skip" (1: with identity extra rows, the grid leaves out the tiles of the structurally zero
  * band instead of launching them to exit at once), "group_eye" (panels per trailing update of the
  * identity-augmented factorisations, gpk_potrf_aug_ex / gpk_nlml_grad; "group" for the others),
@@ -892,10 +903,14 @@ int gpk_chain_plan_ex(int64_t n_pad, int64_t y_row, int32_t grid, int32_t flags,
  * the launches and event edges gpk_potrf_aug / _ex / _ragged enqueue, in order, for this layout when the persistent
  * launch does not apply (gpk_tune "chain"), under the knobs in effect for the calling thread.  flags: those of
  * gpk_potrf_aug_ex.  counters: nonzero if the panel stream has the fused panel solve's ticket counters (every
- * ordinary stream; not hipStreamPerThread or a stream being captured).  kbuild: nonzero for gpk_nlml's factorisation
+ * ordinary stream; not hipStreamPerThread or a stream being captured; without them the stream has no operand scratch
+ * either, so the plan then has no folded panel solve).  The plan is that of a uniform batch: gpk_potrf_aug_ragged runs
+ * the same steps except that it never folds ("ingroup" 4 there is 3).  kbuild: nonzero for gpk_nlml's factorisation
  * with the K build fused into the first trailing update.  One step is GPK_LAUNCH_STEP_WORDS 8-byte words, 21 int64
  * and two doubles:
- *   0 kind (0 diagonal block, 1 panel solve, 2 trailing update, 3 event record, 4 wait for event)
+ *   0 kind (0 diagonal block, 1 panel solve, 2 trailing update, 3 event record, 4 wait for event, 5 the operand of a
+ *     folded panel solve ("ingroup" 4): kblk, the columns [j0, j0 + kdepth) of block row kblk; the panel solve that
+ *     follows it then has kdepth > 128 and also applies the kdepth - 128 columns left of its block column)
  *   1 stream (0 the caller's, 1 panel, 2 bulk; with the look-ahead off every step is on 0)
  *   2 event (record / wait: 0 fork, 1 panel, 2 bulk, 3 join_p, 4 join_b; else -1)
  *   3 role of an update (1 thin, 2 half, 3 look-ahead, 4 bulk, 5 a group's whole trailing update; else 0)
